@@ -11,6 +11,9 @@ polynomials per GPU (default 1024 = BASELINE configs[3]'s per-GPU shard: n=32768
 in HBM when the timed region starts.  Polynomials are independent, so ranks shard the batch with no
 data-path collective (weak scaling); the only collectives are the barrier and the max-over-ranks of the
 elapsed time.  Rank 0 prints ONE JSON line.
+
+--dump-outputs DIR writes, after the timed region, what its last step computed (a fixed sample of the batch, float64 .npy files:
+dump_sample / dump_write); the inputs are generated from fixed seeds, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -142,7 +145,12 @@ def parse():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo lets two ranks share one GPU for a dry run)")
     ap.add_argument("--end-to-end", action="store_true",
                     help="also time scatter -> forward+inverse -> gather from a rank-0-resident batch (SURVEY.md 8(e), report 2)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (a fixed sample, float64: see dump_write)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def synth_recipe(torch, ctx, num, n, device, seed_base):
@@ -159,6 +167,30 @@ def synth(torch, num, n, qs, device, seed):
     a = torch.randint(0, 1 << 60, (num, n), dtype=torch.int64, device=device, generator=g)
     qcol = torch.tensor(qs, dtype=torch.int64, device=device)[torch.arange(num, device=device) % len(qs)].unsqueeze(1)
     return torch.where(a >= qcol, a - qcol, a).contiguous()
+
+
+DUMP_BYTES = 48 << 20       # --dump-outputs: bytes written in all (a fixed sample of whole polynomials when the batch is larger)
+DUMP_SEED = 20240607        # fixes which polynomials the sample holds
+
+
+def dump_sample(torch, outputs, batch, n):
+    """--dump-outputs: the same seeded sample of whole polynomials from each (name, (batch, n) int64 tensor) of `outputs`, as many
+    as fit DUMP_BYTES in all; the sample stays on the device until dump_write"""
+    import numpy as np
+    count = max(1, min(batch, DUMP_BYTES // (len(outputs) * n * 2 * 8)))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(batch, count, replace=False))
+    sel = torch.as_tensor(idx, device=outputs[0][1].device)
+    return [(name, t.index_select(0, sel)) for name, t in outputs], idx
+
+
+def dump_write(directory, sampled):
+    """DIR/<name>.npy per sampled output, float64 of shape (polynomials, n, 2).  A word is a residue of up to 62 bits, wider than a
+    float64 holds exactly, so it is stored as two exact halves: [..., 0] = word >> 32, [..., 1] = word & (2^32 - 1)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, t in sampled:
+        w = t.cpu().numpy().view(np.uint64)
+        np.save(os.path.join(directory, name + ".npy"), np.stack([w >> np.uint64(32), w & np.uint64(0xFFFFFFFF)], axis=-1).astype(np.float64))
 
 
 def cpu_baseline(n, qs, psis):
@@ -532,6 +564,15 @@ def main():
         elapsed, elapsed_min = float(tt[0].item()), -float(tt[1].item())
     step_ms_events = e_beg.elapsed_time(e_end) / args.steps
     assert torch.equal(a, a0)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: `a` after forward_batch + inverse_batch, and the NTT-domain
+        # words forward_batch left in `a` before inverse_batch consumed them -- the same call again on that step's input, which is
+        # a0 (every step is a round trip: asserted above).  Written after the last measurement, so that no figure pays for the copy.
+        fwd = a0.clone()
+        ctx.forward_batch(fwd, batch)
+        dumped = dump_sample(torch, [("forward_batch", fwd), ("forward_inverse", a)], batch, n)
+        del fwd
 
     # ---- per-kernel launch durations: HIP events on the launch stream (torch's current stream) around K back-to-back
     # launches of each kernel (events between every launch of the step loop would serialise the queue and inflate both)
@@ -1042,6 +1083,11 @@ def main():
                              bfv_round_trip(torch, ntt, n, dev, False, DEMO_Q16, DEMO_PSI16, "the 16 primes of demo.cu:35-36 (log q = 880)"),
                              reference_published_v100_us={"keygen": 427.81, "encrypt": 514.73, "decrypt": 246.48, "includes": "samplers",
                                                           "source": "Article.pdf p26 Table 7"})}
+    if dumped is not None:
+        dump_write(args.dump_outputs, dumped[0])
+        out["dump_outputs"] = {"dir": args.dump_outputs, "files": [name + ".npy" for name, _ in dumped[0]],
+                               "polynomials": [int(i) for i in dumped[1]],
+                               "what": "the last timed step's outputs at these batch indices, float64 (polynomials, n, 2): word >> 32, word & (2^32 - 1)"}
     if use_pg:
         out["collective"] = {"backend": dist.get_backend(), "world_size_observed": dist.get_world_size(),
                              "role": "barrier + MAX all-reduce of the timing bracket; scatter / gather of a root-resident batch (end_to_end); no collective on the data path of `value`"}

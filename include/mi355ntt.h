@@ -4,7 +4,7 @@
  * This is the drop-in boundary for the NTT hot path of ozgunozerk/NTT-Cuda.  The reference has no
  * FFI layer: its "operator API" is a set of free functions/kernels in headers that every program
  * textually includes (BFV_Scheme/ntt_60bit.cuh, poly_arithmetic.cuh).  Each entry point below names
- * the reference interface it replaces (paths relative to /root/reference/BFV_Scheme/).
+ * the reference interface it replaces (paths relative to the reference's BFV_Scheme/).
  *
  * Conventions:
  *   - All data pointers are DEVICE pointers to unsigned 64-bit words; plain pointers and sizes only.

@@ -2,7 +2,7 @@
  * ntt_oracle.c -- CPU ORACLE (test infrastructure, NOT product code).  See ntt_oracle.h.
  *
  * Restates, stage by stage and in the reference's own evaluation order, what the CUDA kernels
- * of ozgunozerk/NTT-Cuda compute.  Citations are relative to /root/reference/BFV_Scheme/.
+ * of ozgunozerk/NTT-Cuda compute.  Citations are relative to the reference's BFV_Scheme/.
  * The reference's uint128_t (uint128.h:10-129) is replaced by the compiler's unsigned __int128;
  * SURVEY.md 8(a) lists the host-side quirks of uint128_t that are deliberately NOT reproduced
  * (they never fire for values the reference feeds them).

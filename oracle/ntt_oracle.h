@@ -13,7 +13,7 @@
  * (CUDA + PTX, needs cuda_runtime.h), so there is no oracle/_ref.
  *
  * Every function cites the reference file:line it follows (paths relative to
- * /root/reference/BFV_Scheme/).
+ * the reference's BFV_Scheme/).
  */
 #ifndef NTT_ORACLE_H
 #define NTT_ORACLE_H

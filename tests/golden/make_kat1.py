@@ -1,21 +1,22 @@
 #!/usr/bin/env python3
 """Extract the reference's only known-answer vectors for the NTT hot path into a data fixture.
 
-Source (read in THIS container only; /root/reference does not exist on the GPU box):
-  /root/reference/BFV_Scheme/decryption_test.cu:348  unsigned long long c_host[24576]  (ciphertext c0|pad|c1|pad)
-  /root/reference/BFV_Scheme/decryption_test.cu:355  unsigned long long sk_host[8192]  (secret key, NTT domain)
+Source (a checkout of the reference; the tests read only the fixture this writes):
+  BFV_Scheme/decryption_test.cu:348  unsigned long long c_host[24576]  (ciphertext c0|pad|c1|pad)
+  BFV_Scheme/decryption_test.cu:355  unsigned long long sk_host[8192]  (secret key, NTT domain)
   parameters :26,27,47,48,91 (n, t, q_array, psi_roots, gamma); expected plaintext m[i] = i % 10 (:230-232)
 
 Output: tests/golden/kat1_decryption_n4096.npz  (numbers only: the two arrays + the scalar parameters)
 
-Usage: python tests/golden/make_kat1.py
+Usage: python tests/golden/make_kat1.py <reference checkout>
 """
 import os
 import re
+import sys
 import hashlib
 import numpy as np
 
-SRC = "/root/reference/BFV_Scheme/decryption_test.cu"
+SRC = os.path.join("BFV_Scheme", "decryption_test.cu")         # relative to the reference checkout
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "kat1_decryption_n4096.npz")
 
 
@@ -25,7 +26,9 @@ def grab(text, name):
 
 
 def main():
-    text = open(SRC).read()
+    if len(sys.argv) != 2:
+        sys.exit(__doc__)
+    text = open(os.path.join(sys.argv[1], SRC)).read()
     c = grab(text, "c_host")
     sk = grab(text, "sk_host")
     assert c.size == 24576 and sk.size == 8192, (c.size, sk.size)

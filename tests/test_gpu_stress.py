@@ -266,6 +266,27 @@ def test_soak_checked_raw_calls_follow_the_table_contents(native, oracle, gpu):
     native.raw_cache_clear()
 
 
+# the foreign load of the watchdog test: per line on stdin, that many whole CUs held for 300 ms (mi355ntt_ctx_occupy); "launched"
+# once the kernel is queued, "done" once it has ended
+_WATCHDOG_LOADER = r"""
+import os, sys
+sys.path.insert(0, os.path.join(ROOT, "ntt-cuda_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import torch
+import ntt_cuda_amd as ntt, params as P
+n = 65536
+qs = P.Q60[:2]
+psis = [next(x for x in (pow(g, (q - 1) // (2 * n), q) for g in range(2, 2000)) if pow(x, n, q) == q - 1) for q in qs]
+ctx = ntt.NTTContext(n, qs, psis)
+ctx.occupy(1, 1000); torch.cuda.synchronize()          # (the kernel's first launch -- code object load -- outside the rounds)
+print("ready", flush=True)
+for line in sys.stdin:
+    ctx.occupy(int(line), 300000)
+    print("launched", flush=True)
+    torch.cuda.synchronize()
+    print("done", flush=True)
+ctx.close()
+"""
+
 _WATCHDOG_CHILD = r"""
 import os, sys, time
 sys.path.insert(0, os.path.join(ROOT, "ntt-cuda_amd")); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, ROOT)
@@ -279,7 +300,12 @@ ctx = ntt.NTTContext(n, qs, psis)
 a = torch.empty((num, n), dtype=torch.int64, device=dev); ctx.synth_splitmix(a, num, 5)
 good = a.clone(); ctx.forward_batch(good, num); torch.cuda.synchronize()          # (a normal pair launch first: the reference words)
 cus = torch.cuda.get_device_properties(dev).multi_processor_count
-load, s1 = torch.cuda.Stream(), torch.cuda.Stream()
+s1 = torch.cuda.Stream()
+# The foreign kernel runs in a process of its own.  Two streams of one process may share one hardware queue (GPU_MAX_HW_QUEUES),
+# and the pair launch then waits behind the load in that queue instead of running beside it; two processes never share one.
+import subprocess
+loader = subprocess.Popen([sys.executable, "-c", "ROOT = %r\n" % ROOT + LOADER], stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
+assert loader.stdout.readline().strip() == "ready"
 # (nearly) every CU held for 300 ms: a workgroup of the pair launch that becomes resident while its partner cannot gives up after 20 ms.
 # How many CUs must stay free for ONE workgroup to start is the dispatcher's business (workgroups are dealt to the XCDs round-robin;
 # on the development boxes one free CU starts nothing, two free CUs -- in two XCDs -- start two partner-less workgroups): try a few.
@@ -287,16 +313,20 @@ wrong, gave_up_after, held = False, 0.0, 0
 faults0 = ntt.lib().mi355ntt_pair_fault_count(0)
 for free in (2, 4, 1, 3, 6):
     w = a.clone(); torch.cuda.synchronize()
-    ctx.occupy(cus - free, 300000, stream=load)
+    loader.stdin.write("%d\n" % (cus - free)); loader.stdin.flush()
+    assert loader.stdout.readline().strip() == "launched"
     time.sleep(0.02)
     t0 = time.perf_counter()
     ctx.forward_batch(w, num, stream=s1)
     torch.cuda.synchronize()
     gave_up_after = time.perf_counter() - t0
+    assert loader.stdout.readline().strip() == "done"     # (the load has ended: the next round starts from an idle device)
     wrong = not torch.equal(w, good)
     if wrong:
         held = cus - free
         break
+loader.stdin.close()
+assert loader.wait(timeout=60) == 0
 # the next call that wants the pair slot reports it -- MI355NTT_EHIP, hipErrorLaunchFailure -- launches nothing and clears the condition
 w2 = a.clone(); torch.cuda.synchronize()
 code = hip = None
@@ -317,13 +347,14 @@ ctx.close()
 
 
 def test_pair_watchdog_gives_up_without_killing_the_context(native, gpu):
-    """The cooperating-workgroup launch with all but a few CUs held by a foreign kernel for 300 ms and the watchdog shortened to 20 ms
-    (MI355NTT_PAIR_WATCHDOG_MS): the workgroup that becomes resident never sees its partner, gives up (no trap, no hang: the launch ends
+    """The cooperating-workgroup launch with all but a few CUs held by a foreign kernel (another process) for 300 ms and the watchdog
+    shortened to 20 ms (MI355NTT_PAIR_WATCHDOG_MS): the workgroup that becomes resident never sees its partner, gives up (no trap, no hang: the launch ends
     within the foreign kernel's time, not after 256 x 20 ms -- the other workgroups find the launch marked dead and return), the next
     call reports MI355NTT_EHIP / hipErrorLaunchFailure without touching its data, and the call after that gives the right words again in
     the same process (the round-4 kernels ended in __builtin_trap, which takes the device context along)."""
     env = dict(os.environ, MI355NTT_PAIR_WATCHDOG_MS="20")
-    r = subprocess.run([sys.executable, "-c", "ROOT = %r\n" % ROOT + _WATCHDOG_CHILD], capture_output=True, text=True, timeout=300, env=env)
+    r = subprocess.run([sys.executable, "-c", "ROOT = %r\nLOADER = %r\n" % (ROOT, _WATCHDOG_LOADER) + _WATCHDOG_CHILD], capture_output=True, text=True,
+                       timeout=300, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("WATCHDOG ")][-1]
     f = dict(x.split("=") for x in line.split()[1:])

@@ -1,5 +1,5 @@
 import os, sys, time
-ROOT="/root/repo"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ntt-cuda_amd")); sys.path.insert(0, ROOT)
 import torch, ntt_cuda_amd as ntt
 from bench import Q60, PSI60
