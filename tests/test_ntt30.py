@@ -2,6 +2,8 @@
 import numpy as np
 import pytest
 
+from test_ntt30_moduli import exact_forward30
+
 # getParams30, old/NTT/old_design/final/parameter.h:73-115: n -> (q, psi, psiinv, ninv, q_bit)
 PARAMS30 = {
     2048: (12931073, 3733, 10610200, 12924759, 24),
@@ -40,6 +42,7 @@ def test_oracle30_is_pinned_on_reference_parameters(oracle, n):
     A = oracle.forward30(a, prm)
     if n <= 4096:
         assert np.array_equal(A, exact_forward(a, q, psi, n))          # the transform the reference means
+    assert np.array_equal(A, exact_forward30(a, q, psi, n))            # (the vectorised one at every size)
     assert np.array_equal(oracle.inverse30(A, prm), a)                  # halving butterflies fold n^-1 in
     if n == 2048:                                                       # 30bit_ntt_test.cu's check: schoolbook product
         b = rng.integers(0, q, size=n, dtype=np.uint32)
