@@ -997,7 +997,13 @@ hipError_t launch_mul(int hl, u64* d_a, const u64* d_b, const TwPair* twf, const
 
 
 // explicit per-size entry points (defined in kernels_fast_n<LOGN>.hip)
-#define MI355NTT_DECLARE_SIZE(LOGN)                                                                                               hipError_t fast_fwd_##LOGN(int hl, u64* d_a, const TwPair* tw, const PrimeDev* pr, unsigned num, unsigned division,                                     unsigned base, hipStream_t s);                                                                     hipError_t fast_inv_##LOGN(int hl, u64* d_a, const TwPair* tw, const PrimeDev* pr, unsigned num, unsigned division,                                     unsigned base, hipStream_t s);                                                                     hipError_t fast_mul_##LOGN(int hl, u64* d_a, const u64* d_b, const TwPair* twf, const TwPair* twi, const PrimeDev* pr,                                  unsigned num, unsigned division, hipStream_t s);
+#define MI355NTT_DECLARE_SIZE(LOGN)                                                                                          \
+    hipError_t fast_fwd_##LOGN(int hl, u64* d_a, const TwPair* tw, const PrimeDev* pr, unsigned num, unsigned division,     \
+                               unsigned base, hipStream_t s);                                                                \
+    hipError_t fast_inv_##LOGN(int hl, u64* d_a, const TwPair* tw, const PrimeDev* pr, unsigned num, unsigned division,     \
+                               unsigned base, hipStream_t s);                                                                \
+    hipError_t fast_mul_##LOGN(int hl, u64* d_a, const u64* d_b, const TwPair* twf, const TwPair* twi, const PrimeDev* pr,  \
+                               unsigned num, unsigned division, hipStream_t s);
 MI355NTT_DECLARE_SIZE(11)
 MI355NTT_DECLARE_SIZE(12)
 MI355NTT_DECLARE_SIZE(13)
@@ -1015,6 +1021,21 @@ hipError_t fast_inv_split_16(int hl, u64* d_a, const u64* d_bhat, const TwPair* 
 hipError_t fast_fwd_split_16(int hl, u64* d_a, const TwPair* tw, const PrimeDev* pr, unsigned num, unsigned division, unsigned base,
                              hipStream_t s);
 
-#define MI355NTT_DEFINE_SIZE(LOGN)                                                                                                hipError_t fast_fwd_##LOGN(int hl, u64* d_a, const TwPair* tw, const PrimeDev* pr, unsigned num, unsigned division,                                     unsigned base, hipStream_t s)                                                                      {                                                                                                                                 return launch_fwd<LOGN>(hl, d_a, tw, pr, num, division, base, s);                                                         }                                                                                                                             hipError_t fast_inv_##LOGN(int hl, u64* d_a, const TwPair* tw, const PrimeDev* pr, unsigned num, unsigned division,                                     unsigned base, hipStream_t s)                                                                      {                                                                                                                                 return launch_inv<LOGN>(hl, d_a, tw, pr, num, division, base, s);                                                         }                                                                                                                             hipError_t fast_mul_##LOGN(int hl, u64* d_a, const u64* d_b, const TwPair* twf, const TwPair* twi, const PrimeDev* pr,                                  unsigned num, unsigned division, hipStream_t s)                                                    {                                                                                                                                 return launch_mul<LOGN>(hl, d_a, d_b, twf, twi, pr, num, division, s);                                                    }
+#define MI355NTT_DEFINE_SIZE(LOGN)                                                                                           \
+    hipError_t fast_fwd_##LOGN(int hl, u64* d_a, const TwPair* tw, const PrimeDev* pr, unsigned num, unsigned division,     \
+                               unsigned base, hipStream_t s)                                                                 \
+    {                                                                                                                        \
+        return launch_fwd<LOGN>(hl, d_a, tw, pr, num, division, base, s);                                                    \
+    }                                                                                                                        \
+    hipError_t fast_inv_##LOGN(int hl, u64* d_a, const TwPair* tw, const PrimeDev* pr, unsigned num, unsigned division,     \
+                               unsigned base, hipStream_t s)                                                                 \
+    {                                                                                                                        \
+        return launch_inv<LOGN>(hl, d_a, tw, pr, num, division, base, s);                                                    \
+    }                                                                                                                        \
+    hipError_t fast_mul_##LOGN(int hl, u64* d_a, const u64* d_b, const TwPair* twf, const TwPair* twi, const PrimeDev* pr,  \
+                               unsigned num, unsigned division, hipStream_t s)                                               \
+    {                                                                                                                        \
+        return launch_mul<LOGN>(hl, d_a, d_b, twf, twi, pr, num, division, s);                                               \
+    }
 
 }  // namespace mi355ntt

@@ -227,9 +227,6 @@ constexpr unsigned kPair30MinPolysFwd = 32, kPair30MinPolysInv = 384;
 template <int BO, int BN>
 __device__ __forceinline__ void exchange32(u32 (&v)[32], u32* img, unsigned t)
 {
-#ifdef NTT30_NOEX                                         // timing experiment: no workgroup exchange
-    return;
-#endif
     __builtin_amdgcn_sched_barrier(0);
     // DS instructions carry a 16-bit byte offset: the image (up to 132 KiB) is addressed through three bases 64 KiB apart,
     // pinned so that the compiler does not materialise one address per register
@@ -332,18 +329,12 @@ __device__ __forceinline__ void rows_to_layout0_32(u32 (&v)[32], u32* img, unsig
 // Twiddles of butterfly group G of a round: 8 butterflies per group, two groups per stage, the loads run one group ahead
 // (a ring of 2 x 8 pairs = 32 VGPRs); scheduling fences around each group keep the compiler from hoisting a whole round's
 // loads (which cost the first version 144 VGPRs and spills).
-#ifndef NTT30_GROUP
-#define NTT30_GROUP 8
-#endif
-constexpr int GROUP32 = NTT30_GROUP, GPS32 = 16 / GROUP32;      // butterflies per twiddle group, groups per stage
+constexpr int GROUP32 = Tune::kNtt30Group, GPS32 = 16 / GROUP32;      // butterflies per twiddle group, groups per stage
 
 // n = 2^15: the twiddles of the middle round (register field at bit 5: stage blocks 32 ... 512, 992 pairs = 8 KiB, two
 // distinct addresses per wave) stay in LDS for the life of the persistent workgroup -- one modulus per call, so every
 // polynomial of the workgroup uses the same ones.  That takes half of the vector twiddle loads off the vector-memory
 // counter: the middle round then never waits behind the prefetch of the next polynomial (results return in order).
-#ifndef NTT30_LDS_TW
-#define NTT30_LDS_TW 1
-#endif
 __device__ __forceinline__ uint2* tw2_lds()
 {
     __shared__ uint2 buf[1024];
@@ -354,16 +345,12 @@ __device__ __forceinline__ void load_tw32(uint2 (&W)[GROUP32], const uint2* __re
 {
     constexpr int j = FWD ? JA - G / GPS32 : JA + G / GPS32;
     constexpr unsigned len = 1u << (LOGN - 1 - (B + j));
-#ifdef NTT30_NOTW                                         // timing experiment (tools/kbench30.hip): no twiddle loads
-    static_for<GROUP32>([&](auto kc) { W[decltype(kc)::value] = make_uint2(12345u + thi, 54321u + tmul); });
-    return;
-#endif
     if constexpr (B == Geo<LOGN>::B0) {                  // first / last round: the group index does not depend on the thread -> scalar loads
         static_for<GROUP32>([&](auto kc) {
             constexpr int r0 = low_reg(j, (G % GPS32) * GROUP32 + decltype(kc)::value);
             W[decltype(kc)::value] = tw[len * tmul + ((unsigned)r0 >> (j + 1))];
         });
-    } else if constexpr (NTT30_LDS_TW && LOGN == 15 && B == 5) {      // the workgroup's LDS copy (k_ntt30x fills it once): index as in the table, tmul folded in
+    } else if constexpr (Tune::kNtt30LdsTw && LOGN == 15 && B == 5) {      // the workgroup's LDS copy (k_ntt30x fills it once): index as in the table, tmul folded in
         const uint2* lt = tw2_lds() + len + (thi << (4 - j));
         static_for<GROUP32>([&](auto kc) {
             constexpr int r0 = low_reg(j, (G % GPS32) * GROUP32 + decltype(kc)::value);
@@ -508,11 +495,6 @@ __device__ __forceinline__ void inv_rounds32(u32 (&v)[32], const uint2* tw, BufR
     }
 }
 
-// start stagger of the persistent workgroups (forward kernel only; measured at 4096 polynomials of 2^15 words: +3 % with
-// 2 units, nothing on the inverse)
-#ifndef NTT30_STAGGER
-#define NTT30_STAGGER 2
-#endif
 // One workgroup of 2^LOGN / 32 threads per polynomial of 2^LOGN words, persistent over the batch.  split: the polynomials
 // are the halves of 2^(LOGN+1)-word polynomials whose first (forward) / last (inverse) stage runs as a stage launch.
 // PAIR (forward, split: the polynomials are the halves of 2^(LOGN+1)-word polynomials): no stage launch in front.  Two
@@ -560,10 +542,6 @@ k_ntt30x(u32* __restrict__ a, const Scratch30* __restrict__ sc, u32 q, unsigned 
     [[maybe_unused]] u32 nv[PAIR ? 32 : 1];
     auto issue_loads = [&](unsigned y, bool real) {
         const BufRsrc rs = make_rsrc(a + (size_t)(PAIR && FWD ? y & ~1u : y) * n, real ? n * 4u : 0u);      // (PAIR forward: the lower half U)
-#if defined(NTT30_NOMEM) || defined(NTT30_NOLOAD)         // timing experiment: no polynomial traffic
-        static_for<32>([&](auto rc) { nx[decltype(rc)::value] = (t + decltype(rc)::value + y) & 0xffffu; });
-        return;
-#endif
         if constexpr (FWD)
             static_for<32>([&](auto rc) { nx[decltype(rc)::value] = __builtin_amdgcn_raw_buffer_load_b32(rs, t * 4u, ((unsigned)decltype(rc)::value << G::B0) * 4u, 0); });
         else
@@ -581,13 +559,13 @@ k_ntt30x(u32* __restrict__ a, const Scratch30* __restrict__ sc, u32 q, unsigned 
         else
             static_for<32>([&](auto rc) { __builtin_amdgcn_raw_buffer_store_b32(v[decltype(rc)::value], prs, t * 4u, ((unsigned)decltype(rc)::value << G::B0) * 4u, 0); });
     };
-#if NTT30_STAGGER > 0
-    // every workgroup runs the same schedule; 8 phase groups per XCD start NTT30_STAGGER x 2048 cycles apart
-    if (FWD && gridDim.x >= 256u)                          // (PAIR: partners start together)
-        for (unsigned i = 0; i < ((blockIdx.x >> (PAIR ? 4 : 3)) & 7u) * NTT30_STAGGER; i++) __builtin_amdgcn_s_sleep(32);
-#endif
+    if constexpr (Tune::kNtt30Stagger > 0) {
+        // every workgroup runs the same schedule; 8 phase groups per XCD start Tune::kNtt30Stagger x 2048 cycles apart
+        if (FWD && gridDim.x >= 256u)                      // (PAIR: partners start together)
+            for (unsigned i = 0; i < ((blockIdx.x >> (PAIR ? 4 : 3)) & 7u) * Tune::kNtt30Stagger; i++) __builtin_amdgcn_s_sleep(32);
+    }
     if (first >= num) return;
-    if constexpr (NTT30_LDS_TW && LOGN == 15) {          // middle-round twiddles into LDS (read only after the first exchange's barriers)
+    if constexpr (Tune::kNtt30LdsTw && LOGN == 15) {     // middle-round twiddles into LDS (read only after the first exchange's barriers)
         const unsigned tm = split ? 2u + (first & 1u) : 1u;
         for (unsigned i = 32u + t; i < 1024u; i += G::T) {
             const unsigned l0 = 1u << (31u - __clz(i));
@@ -651,15 +629,7 @@ k_ntt30x(u32* __restrict__ a, const Scratch30* __restrict__ sc, u32 q, unsigned 
                 asm volatile("" ::: "memory");            // (compiler-level order: no store of the result moves above the poll)
                 it++;
             }
-#if !defined(NTT30_NOMEM) && !defined(NTT30_NOSTORE)
             issue_stores(prs);
-#else
-            {
-                u32 x = 0;                                // (keeps every output alive)
-                static_for<32>([&](auto rc) { x ^= v[decltype(rc)::value] + decltype(rc)::value; });
-                if (x == 0xdeadbeefu) a[t] = x;
-            }
-#endif
         } else {
             __syncthreads();                             // (the previous polynomial's last exchange has been read)
             rows_to_layout0_32(v, img, t);
@@ -710,15 +680,7 @@ k_ntt30x(u32* __restrict__ a, const Scratch30* __restrict__ sc, u32 q, unsigned 
                 }
                 it++;
             } else {
-#if !defined(NTT30_NOMEM) && !defined(NTT30_NOSTORE)
-            issue_stores(prs);
-#else
-            {
-                u32 x = 0;                                // (keeps every output alive)
-                static_for<32>([&](auto rc) { x ^= v[decltype(rc)::value] + decltype(rc)::value; });
-                if (x == 0xdeadbeefu) a[t] = x;
-            }
-#endif
+                issue_stores(prs);
             }
         }
     }

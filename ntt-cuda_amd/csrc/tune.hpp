@@ -1,11 +1,13 @@
-// tune.hpp -- the tuning constants of the single-pass kernels (ntt_core.cuh, kernels_fast_impl.cuh, kernels_lat.cuh), in ONE place.
+// tune.hpp -- the tuning constants of the single-pass kernels (ntt_core.cuh, kernels_fast_impl.cuh, kernels_lat.cuh, kernels_ntt30.hip),
+// in ONE place.
 //
 // Rounds 1-5 carried ~55 compile-time experiment switches inside the kernel sources (ablations that produced wrong results,
 // in-kernel time stamps, alternative code paths); round 6 froze the kernels and removed all of them.  What is
 // left is this struct: plain values the kernels read as template arguments / constants.  The library always builds with the values
 // below.  A measurement build (tools/build_kbench.sh) may substitute another struct of the same shape by defining
 // MI355NTT_TUNE_HEADER to the path of a header that defines `mi355ntt::Tune`; nothing else in csrc/ looks at a macro to change a
-// kernel.  The ablation / stamp builds behind profiles/r01..r05_* are reproducible from the round-5 tree (commit 3b06c3b).
+// kernel.  The ablation / stamp builds behind profiles/r01..r05_* are reproducible from the round-5 tree (commit 3b06c3b); the 30-bit
+// ablations behind profiles/r0*_ntt30* (tools/kbench30.hip) from commit bbd478d.
 //
 // Each value names the profile that chose it.
 #pragma once
@@ -42,6 +44,10 @@ struct Tune {
     static constexpr int kTwoPhaseMinLogN = 13; // half-size LDS image (two-phase exchange) from n = 2^13 up
     static constexpr bool kFwdLoadPair16 = true;      // forward loads issued in consumption order (0, 16, 1, 17, ...): +0.8 %
     static constexpr bool kInvDescending = true;      // k_inverse15 walks the batch from the last polynomial down: +2.5 % pairs at 1024 (profiles/r02_walk_order_and_store_policy.txt)
+    // ---- the 30-bit native kernel k_ntt30x (kernels_ntt30.hip; profiles/r02_ntt30_native_kernels.txt, section C)
+    static constexpr int kNtt30Group = 8;             // butterflies per twiddle group, loads one group ahead (ring of 2 x 8 pairs = 32 VGPRs; a whole round's loads hoisted: 144 VGPRs and spills)
+    static constexpr bool kNtt30LdsTw = true;         // n = 2^15: middle-round twiddles resident in LDS, filled once per workgroup: inverse +13 %
+    static constexpr int kNtt30Stagger = 2;           // start stagger of the forward kernel's workgroups, units x 2048 cycles: +3 % with 2 units at 4096 polynomials, nothing on the inverse
 };
 }  // namespace mi355ntt
 #endif

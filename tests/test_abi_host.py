@@ -120,34 +120,50 @@ def test_product_never_imports_oracle():
 
 
 def test_kernel_sources_carry_no_experiment_switches():
-    """the lab left the product.  The kernel sources hold no conditional compilation on an MI355NTT_* macro (rounds
-    1-5 carried ~55 of them: ablations that produced wrong results, in-kernel stamps, alternative code paths); the tuning VALUES live in
-    ONE struct, csrc/tune.hpp, which is also the only place a measurement build can hook into (MI355NTT_TUNE_HEADER)."""
+    """the lab left the product.  No kernel source holds conditional compilation on a macro of its own (rounds
+    1-5 carried ~55 such switches: ablations that produced wrong results, in-kernel stamps, alternative code paths; the 30-bit path
+    kept NTT30_* ablations until VERDICT r06 item 5); the tuning VALUES live in ONE struct, csrc/tune.hpp, which is also the only
+    place a measurement build can hook into (MI355NTT_TUNE_HEADER).  Every file of csrc/ is read: the only conditional lines are
+    the HIP-compiler guard of kernels.hpp and that hook."""
     csrc = os.path.join(ROOT, "ntt-cuda_amd", "csrc")
-    for f in ("ntt_core.cuh", "kernels_fast_impl.cuh", "kernels_lit.cuh", "kernels_lat.cuh", "modarith.cuh"):
+    allowed = {("kernels.hpp", "#ifdef __HIPCC__"), ("tune.hpp", "#ifdef MI355NTT_TUNE_HEADER")}
+    files = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".cuh", ".hpp", ".cpp")))
+    assert {"kernels_ntt30.hip", "kernels_fast_n16.hip", "ntt_core.cuh", "tune.hpp"} <= set(files), files
+    found = set()
+    for f in files:
         t = open(os.path.join(csrc, f)).read()
-        cond = [l for l in t.splitlines() if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", l)]
-        assert not cond, (f, cond[:5])
-        assert not re.search(r"MI355NTT_(ABLATE|STAMP|TOUCH|LAB|POLY_SLOT|ONLY_HL4N)", t), f
+        cond = {(f, l.strip()) for l in t.splitlines() if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", l)}
+        assert cond <= allowed, (f, sorted(cond - allowed)[:5])
+        found |= cond
+        assert not re.search(r"MI355NTT_(ABLATE|STAMP|TOUCH|LAB|POLY_SLOT|ONLY_HL4N|N16_NO_CLASS35)", t), f
+        assert "NTT30_" not in t, f
+    assert found == allowed, found
     tune = open(os.path.join(csrc, "tune.hpp")).read()
     assert tune.count("#ifdef") == 1 and "MI355NTT_TUNE_HEADER" in tune and "struct Tune" in tune
 
 
+def _device_asm(tmp_path, tag, src, flags):
+    """gfx950 assembly of one translation unit, without comments, file names and the per-compilation id"""
+    inc = ["-I", os.path.join(ROOT, "ntt-cuda_amd", "csrc"), "-I", os.path.join(ROOT, "include")]
+    out = tmp_path / (tag + ".s")
+    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only"] + inc + flags
+                       + [str(src), "-o", str(out)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return [l for l in open(out).read().splitlines() if not l.lstrip().startswith((";", ".ident", ".file")) and "__hip_cuid" not in l]
+
+
 def test_stray_defines_do_not_change_a_kernel(tmp_path):
-    """A -DMI355NTT_... left in CXXFLAGS can no longer ship a different kernel: the same translation unit compiled with and without a
-    handful of the former switches yields the same gfx950 assembly."""
+    """A -D left in CXXFLAGS can no longer ship a different kernel: the same translation unit compiled with and without a handful of
+    the former switches yields the same gfx950 assembly -- one 60-bit kernel, and the whole 30-bit path (kernels_ntt30.hip, about
+    20 s) against its former ablations and tuning overrides."""
     src = tmp_path / "probe.hip"
     src.write_text('#include "kernels_fast_impl.cuh"\nnamespace mi355ntt {\n'
                    'template __global__ void k_forward<11, 4, true>(u64*, const TwPair*, const PrimeDev*, unsigned, unsigned, unsigned);\n}\n')
-    inc = ["-I", os.path.join(ROOT, "ntt-cuda_amd", "csrc"), "-I", os.path.join(ROOT, "include")]
-    base = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only"] + inc
-    outs = []
-    for k, flags in enumerate(([], ["-DMI355NTT_ABLATE_EXCHANGE", "-DMI355NTT_STAMPS=1", "-DMI355NTT_PRIO_R1=2", "-DMI355NTT_MAD_CHAIN=0", "-DMI355NTT_LAB"])):
-        out = tmp_path / ("k%d.s" % k)
-        r = subprocess.run(base + flags + [str(src), "-o", str(out)], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-2000:]
-        outs.append([l for l in open(out).read().splitlines() if not l.lstrip().startswith((";", ".ident", ".file")) and "__hip_cuid" not in l])
-    assert outs[0] == outs[1]
+    flags = ["-DMI355NTT_ABLATE_EXCHANGE", "-DMI355NTT_STAMPS=1", "-DMI355NTT_PRIO_R1=2", "-DMI355NTT_MAD_CHAIN=0", "-DMI355NTT_LAB"]
+    assert _device_asm(tmp_path, "k0", src, []) == _device_asm(tmp_path, "k1", src, flags)
+    src30 = os.path.join(ROOT, "ntt-cuda_amd", "csrc", "kernels_ntt30.hip")
+    flags30 = ["-DNTT30_NOEX", "-DNTT30_NOTW", "-DNTT30_NOMEM", "-DNTT30_NOSTORE", "-DNTT30_GROUP=4", "-DNTT30_LDS_TW=0", "-DNTT30_STAGGER=0"]
+    assert _device_asm(tmp_path, "n0", src30, []) == _device_asm(tmp_path, "n1", src30, flags30)
 
 
 @pytest.fixture(scope="module")

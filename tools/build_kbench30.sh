@@ -1,5 +1,7 @@
 #!/bin/bash
 # usage: tools/build_kbench30.sh <tag> [extra hipcc flags...]  -> tools/kbench30_<tag>; prints register use of the n = 2^15 kernels
+# A variant build substitutes the tuning struct: -DMI355NTT_TUNE_HEADER='"/path/to/my_tune.hpp"' (a header that defines mi355ntt::Tune
+# with the members of ntt-cuda_amd/csrc/tune.hpp, kNtt30* among them); the kernel sources themselves carry no switches.
 R=$(cd "$(dirname "$0")/.." && pwd)
 tag=$1; shift
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -I $R/ntt-cuda_amd/csrc -I $R/include "$@" $R/tools/kbench30.hip \

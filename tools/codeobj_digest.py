@@ -3,7 +3,8 @@
 shipped instantiation is byte-identical before and after").
 
 usage: python tools/codeobj_digest.py OBJECT [OBJECT ...]      -> one line per kernel: sha256 of its instruction stream, size, name
-       python tools/codeobj_digest.py --diff OLD NEW           -> kernels whose code differs / appeared / disappeared (exit 1 if any differ)
+       python tools/codeobj_digest.py --diff OLD NEW           -> kernels whose code differs / appeared / disappeared (exit 1 if any differ,
+                                                                  or if two kernels of one input normalise to the same name)
        python tools/codeobj_digest.py --loose --diff OLD NEW   -> the same comparison modulo scalar-register allocation (see loosen)
 
 The instruction stream is the disassembly (llvm-objdump -d of the unbundled gfx950 code object) with addresses and encodings
@@ -73,6 +74,9 @@ def digests(path):
             def flush():
                 if name and body and not name.startswith("__hip_cuid"):
                     h = hashlib.sha256("\n".join(body).encode()).hexdigest()
+                    # (a template instantiated in two translation units is one kernel: the same code under the same symbol)
+                    if res.get(name, (h, len(body))) != (h, len(body)):
+                        raise SystemExit("%s: two different kernels named %s" % (path, name))
                     res[name] = (h, len(body))
             for line in dis.splitlines():
                 m = re.match(r"^[0-9a-f]* ?<(.+)>:$", line.strip())
@@ -90,11 +94,17 @@ def digests(path):
     return res
 
 
+def short_names(d):
+    """the demangled names of d's kernels without namespaces, return type and argument list: `k_ntt30x<15, true, false>`"""
+    names = subprocess.run(["c++filt"], input="\n".join(d), capture_output=True, text=True).stdout.splitlines()
+    # ("(anonymous namespace)::" goes first: the cut at the first "(" would otherwise leave every such kernel nameless)
+    return [re.sub(r"\(.*", "", nm.replace("(anonymous namespace)::", "")).replace("void ", "").replace("mi355ntt::", "") for nm in names]
+
+
 def named_digests(path):
     """{demangled kernel name: sha256 of its instruction stream} of one object / library"""
     d = digests(path)
-    names = subprocess.run(["c++filt"], input="\n".join(d), capture_output=True, text=True).stdout.splitlines()
-    return {re.sub(r"\(.*", "", nm).replace("void ", "").replace("mi355ntt::", ""): h for (raw, (h, n)), nm in zip(d.items(), names)}
+    return {nm: h for (h, n), nm in zip(d.values(), short_names(d))}
 
 
 def main():
@@ -108,17 +118,20 @@ def main():
             old.update(digests(p))
         for p in args[2].split(","):
             new.update(digests(p))
+        collisions = []
         def by_name(d):
-            names = subprocess.run(["c++filt"], input="\n".join(d), capture_output=True, text=True).stdout.splitlines()
             out = {}
-            for (raw, v), nm in zip(d.items(), names):
-                nm = re.sub(r"\(.*", "", nm).replace("void ", "").replace("mi355ntt::", "")
+            for v, nm in zip(d.values(), short_names(d)):
                 # (round 6 appended a defaulted template argument CHECKED = false to k_forward15 / k_inverse15: the same kernels)
                 nm = re.sub(r"^(k_forward15<\d, (?:true|false), \d), false>$", r"\1>", nm)
                 nm = re.sub(r"^(k_inverse15<\d, (?:true|false)), false>$", r"\1>", nm)
+                if nm in out:
+                    collisions.append(nm)
                 out[nm] = v
             return out
         old, new = by_name(old), by_name(new)
+        for nm in collisions:
+            print("COLLIDES         %s" % nm)
         bad = 0
         for raw in sorted(set(old) | set(new)):
             nm = raw
@@ -129,13 +142,13 @@ def main():
             elif old[raw][0] != new[raw][0]:
                 print("DIFFERS  %6d -> %6d  %s" % (old[raw][1], new[raw][1], nm))
                 bad += 1
-        print("%d kernels compared, %d differ" % (len(set(old) & set(new)), bad))
-        sys.exit(1 if bad else 0)
+        print("%d kernels compared, %d differ" % (len(set(old) & set(new)), bad)
+              + (", %d names collide" % len(collisions) if collisions else ""))
+        sys.exit(1 if bad or collisions else 0)
     for p in args:
         d = digests(p)
-        names = subprocess.run(["c++filt"], input="\n".join(d), capture_output=True, text=True).stdout.splitlines()
-        for (raw, (h, n)), nm in zip(d.items(), names):
-            print("%s %6d  %s" % (h[:16], n, re.sub(r"\(.*", "", nm).replace("void ", "").replace("mi355ntt::", "")))
+        for (h, n), nm in zip(d.values(), short_names(d)):
+            print("%s %6d  %s" % (h[:16], n, nm))
 
 
 if __name__ == "__main__":

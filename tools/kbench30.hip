@@ -1,5 +1,5 @@
-// Stand-alone timing of the 30-bit native kernels (k_ntt30x) with compile-time ablations; timing only (tables are random
-// words below q).  Build: tools/build_kbench30.sh <tag> [-DNTT30_...]; run: tools/kbench30_<tag> [logn] [num] [reps]
+// Stand-alone timing of the 30-bit native kernels (k_ntt30x); timing only (tables are random words below q).
+// Build: tools/build_kbench30.sh <tag> [hipcc flags]; run: tools/kbench30_<tag> [logn] [num] [reps]
 #include "../ntt-cuda_amd/csrc/kernels_ntt30.hip"
 #include <algorithm>
 #include <cstdio>

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """n = 65536: throughput of the one-launch forms per kernel class (round 5: classes 5 and 3 have split kernels of their own).
-usage: python tools/sweep_classes16.py [num=512]   (GPU; MI355NTT_N16_NO_CLASS35=1 in the environment folds classes 5 / 3 into 4 / 2)"""
+usage: python tools/sweep_classes16.py [num=512]   (GPU)"""
 import os
 import sys
 
@@ -26,7 +26,7 @@ def near_primes(k, count):
     return out
 
 
-print("# n = 65536, %d polynomials per launch, context API, warm, back to back%s" % (num, "  [classes 5 / 3 folded into 4 / 2]" if os.environ.get("MI355NTT_N16_NO_CLASS35") else ""))
+print("# n = 65536, %d polynomials per launch, context API, warm, back to back" % num)
 print("# class                kernel class   fwd ms    inv ms   product ms   TB/s fwd  TB/s inv")
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 for name, k in (("hl4-near 60-bit", 60), ("hl5-near 59-bit", 59), ("hl3-near 61-bit", 61), ("hl2-near 62-bit", 62), ("hl6-near 58-bit", 58)):
