@@ -395,6 +395,65 @@ int mi355ntt_bfv_keygen_rns(const mi355ntt_bfv* bfv, void* d_in, mi355ntt_u64* d
 int mi355ntt_bfv_encryption_rns(const mi355ntt_bfv* bfv, mi355ntt_u64* d_c, const mi355ntt_u64* d_public_key, void* d_in,
                                 mi355ntt_u64* d_e, const mi355ntt_u64* d_m, mi355ntt_u64 nonce, mi355ntt_stream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * BFV evaluation: ciphertext + ciphertext, - ciphertext, x ciphertext and relinearization, on the ciphertexts the drivers above
+ * write and read (coefficient domain, [2][count][num_primes][n], r = num_primes - 1 primes q_0 .. q_{r-1} form Q, the special
+ * prime's slot unused).  Multiplication is the full-RNS BEHZ form (Bajard, Eynard, Hasan, Zucca, SAC 2016): the operands are
+ * extended from Q to B_sk = B u {m_sk} (|B| = r auxiliary primes, m_sk one more) with m~ = 2^32, multiplied in the NTT domain over
+ * Q u B_sk, scaled by t / Q with a fast floor into B_sk and brought back to Q exactly (Shenoy-Kumaresan).  Relinearization splits d2
+ * into its r RNS digits D_i = [d2]_{q_i} against the key rlk_i = (-(a_i s + e_i) + s^2 g_i, a_i), g_i = 1 mod q_i, 0 mod q_j (j != i).
+ *
+ * The evaluator owns two contexts, over Q and over B_sk, both created with MI355NTT_CTX_EXACT_ON_INEXACT_PRIMES: its arithmetic is
+ * exact whatever the BFV object's moduli (a BFV object on a Barrett-inexact prime included).  It is immutable after creation, keeps a
+ * pointer to the BFV object (which must outlive it), and runs on that object's device (the caller's device is restored).
+ *
+ * Semantics shared by every call below:
+ *   - count = 1 is the single-ciphertext layout [2][num_primes][n]; batches are component-major as in the batched drivers.
+ *   - Outputs leave the special prime's slot untouched.
+ *   - An input word equal to q_i (the reference's `>` reductions leave such words for 0) is read as 0.
+ *   - Every argument is checked before any memory is touched: NULL pointers (d_scratch included) and count = 0 give
+ *     MI355NTT_EINVAL, count > 65535 MI355NTT_EUNSUPPORTED.
+ *   - Nothing allocates or synchronises; scratch comes from the caller (mi355ntt_bfv_eval_scratch_bytes for `count`).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct mi355ntt_bfv_eval mi355ntt_bfv_eval;
+/* host only: the r + 1 auxiliary primes of B_sk for ring degree n (m_sk last) and a primitive 2n-th root of each: the largest primes
+ * p = 1 (mod 2n) below 2^61 on which the reference's Barrett is exact (mi355ntt_barrett_is_exact).  1 <= r <= 15. */
+int mi355ntt_bfv_aux_primes(unsigned n, unsigned r, mi355ntt_u64* b, mi355ntt_u64* psi_b);
+/* MI355NTT_EUNSUPPORTED for parameter sets outside the size condition of DESIGN.md ("BFV evaluation"): every q_i < 2^61 and
+ * sum bits(q_i) + log2 n + log2 t + 3 <= sum (bits(b_j) - 1) */
+int mi355ntt_bfv_eval_create(mi355ntt_bfv_eval** out, const mi355ntt_bfv* bfv);
+int mi355ntt_bfv_eval_destroy(mi355ntt_bfv_eval* ev);
+/* the r + 1 primes of B_sk this evaluator uses (host array): mi355ntt_bfv_aux_primes's, with any candidate equal to one of the BFV
+ * object's primes skipped */
+int mi355ntt_bfv_eval_aux_primes(const mi355ntt_bfv_eval* ev, mi355ntt_u64* b);
+/* bytes of d_scratch a call with `count` ciphertexts needs (the same for every call below) */
+size_t mi355ntt_bfv_eval_scratch_bytes(const mi355ntt_bfv_eval* ev, unsigned count);
+/* relinearization key rlk [r][2][num_primes][n], NTT domain over Q.  d_secret_key: keygen's NTT-domain key [num_primes][n];
+ * d_a [r][num_primes][n]: uniform residues, taken as NTT-domain values (as keygen takes the public key's second half);
+ * d_e [r][num_primes][n]: error samples as residues, coefficient domain.  The special slot of rlk is not written. */
+int mi355ntt_bfv_relin_keygen(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_rlk, const mi355ntt_u64* d_secret_key,
+                              const mi355ntt_u64* d_a, const mi355ntt_u64* d_e, mi355ntt_stream stream);
+/* the complete form: Salsa20 keystream (a key of its own, 32 x 0x02, distinct from keygen_rns's 32 x 0x01, so that no nonce makes a
+ * relinearization key repeat keygen's samples; the caller's nonce) of r * mi355ntt_bfv_keygen_random_bytes(bfv) bytes into
+ * d_in (16-byte aligned), keygen's uniform / Gaussian conversions per key (mi355ntt_bfv_sample_keygen; its ternary output goes to
+ * d_temp [num_primes][n] and is discarded), then the above.  Writes the special slot of rlk. */
+int mi355ntt_bfv_relin_keygen_rns(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_rlk, const mi355ntt_u64* d_secret_key,
+                                  void* d_in, mi355ntt_u64* d_temp, mi355ntt_u64 nonce, mi355ntt_stream stream);
+/* d_c = d_a +/- d_b, ciphertexts [2][count][num_primes][n]; d_c may alias d_a or d_b */
+int mi355ntt_bfv_add(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_b, unsigned count,
+                     mi355ntt_stream stream);
+int mi355ntt_bfv_sub(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_b, unsigned count,
+                     mi355ntt_stream stream);
+/* tensor product and t / Q rescale: d_c3 [3][count][num_primes][n] */
+int mi355ntt_bfv_multiply(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c3, const mi355ntt_u64* d_a, const mi355ntt_u64* d_b,
+                          unsigned count, void* d_scratch, mi355ntt_stream stream);
+/* d_c [2][count][num_primes][n] from d_c3 [3][count][num_primes][n]; d_c may alias d_c3 */
+int mi355ntt_bfv_relinearize(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_c3, const mi355ntt_u64* d_rlk,
+                             unsigned count, void* d_scratch, mi355ntt_stream stream);
+/* multiply then relinearize; d_c may alias d_a or d_b */
+int mi355ntt_bfv_multiply_relin(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_b,
+                                const mi355ntt_u64* d_rlk, unsigned count, void* d_scratch, mi355ntt_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,3 +76,14 @@ hipError_t bfv_decrypt_scale(const BfvParams& p, const BfvDevice& d, u64* c, hip
 hipError_t bfv_decrypt_round(const BfvParams& p, const BfvDevice& d, u64* c, hipStream_t s, unsigned count = 1);
 
 }  // namespace mi355ntt
+
+// the BFV object behind the C ABI handle (bfv_host.cpp; the evaluator of bfv_eval_host.cpp reads its parameters)
+struct mi355ntt_bfv {
+    mi355ntt_ctx* ntt = nullptr;
+    mi355ntt::BfvParams p;
+    mi355ntt::BfvDevice d;
+    void* d_prime = nullptr;
+    void* d_bcm = nullptr;
+    void* d_epi = nullptr;        // [R] BfvEpiPrime: the epilogue constants of the batched decryption
+    bool epi_ok = false;          // the one-product form of the scaling is the reference's words for these moduli
+};

@@ -1,0 +1,418 @@
+// bfv_eval_host.cpp -- the BFV evaluator (C ABI section "BFV evaluation" of include/mi355ntt.h): auxiliary prime search, BEHZ
+// constants, relinearization key generation and the drivers.  Transforms run through the evaluator's two exact contexts (one over
+// Q, one over B_sk); the element-wise RNS steps through kernels_bfv_eval.hip.  DESIGN.md, "BFV evaluation", states the algorithm
+// and the bounds the constants below rely on.
+#include "../../include/mi355ntt.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+#include <new>
+
+#include "bfv.hpp"
+#include "bfv_eval.hpp"
+#include "device_scope.hpp"
+
+using namespace mi355ntt;
+
+namespace mi355ntt {
+void record_hip_error(int e);      // capi.cpp: what mi355ntt_last_hip_error() reports
+}
+
+namespace {
+
+// deterministic Miller-Rabin for every 64-bit n (the first twelve primes as bases suffice below 3.3e24)
+bool is_prime64(u64 n)
+{
+    if (n < 2) return false;
+    static const u64 small[] = {2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37};
+    for (u64 p : small)
+        if (n % p == 0) return n == p;
+    u64 d = n - 1;
+    unsigned s = 0;
+    while ((d & 1) == 0) {
+        d >>= 1;
+        s++;
+    }
+    for (u64 a : small) {
+        u64 x = modpow(a, d, n);
+        if (x == 1 || x == n - 1) continue;
+        bool composite = true;
+        for (unsigned i = 1; i < s && composite; i++) {
+            x = mulmod(x, x, n);
+            if (x == n - 1) composite = false;
+        }
+        if (composite) return false;
+    }
+    return true;
+}
+
+// the r + 1 largest primes p = 1 (mod 2n) below 2^61 on which the reference's Barrett is exact and that are not in excl[0..nexcl);
+// psi: x^((p - 1) / 2n) for the first x = 2, 3, ... with psi^n = -1
+int aux_primes(unsigned n, unsigned r, const u64* excl, unsigned nexcl, u64* b, u64* psi_b)
+{
+    if (n < 2048 || n > 65536 || (n & (n - 1)) != 0) return MI355NTT_EUNSUPPORTED;
+    if (r < 1 || r > kEvalMaxQ) return MI355NTT_EUNSUPPORTED;
+    const u64 step = 2ull * n;
+    unsigned found = 0;
+    for (u64 p = (1ull << 61) - step + 1; found < r + 1 && p > (1ull << 60); p -= step) {
+        bool skip = false;
+        for (unsigned i = 0; i < nexcl; i++) skip |= excl[i] == p;
+        if (skip || !is_prime64(p)) continue;
+        const unsigned k = bit_length(p);
+        if (!barrett_single_subtraction_exact(p, k, barrett_mu(p, k))) continue;
+        u64 psi = 0;
+        for (u64 x = 2; x < 1000 && !psi; x++) {
+            const u64 w = modpow(x, (p - 1) / step, p);
+            if (modpow(w, n, p) == p - 1) psi = w;
+        }
+        if (!psi) continue;
+        b[found] = p;
+        if (psi_b) psi_b[found] = psi;
+        found++;
+    }
+    return found == r + 1 ? MI355NTT_OK : MI355NTT_EUNSUPPORTED;
+}
+
+EvPrime ev_prime(u64 q)
+{
+    EvPrime e;
+    e.q = q;
+    e.m64 = ~0ULL / q;
+    e.r64 = (u64)((((u128)1) << 64) % q);
+    e.r64p = shoup(e.r64, q);
+    return e;
+}
+
+u64 inv_mod_2_32(u64 a)       // a odd
+{
+    u64 x = a;                // Newton: each step doubles the correct low bits (3 -> 6 -> 12 -> 24 -> 48)
+    for (int i = 0; i < 5; i++) x *= 2 - a * x;
+    return x & 0xffffffffull;
+}
+
+// product of m[0..cnt) except m[skip] (skip = cnt: all of them), mod p
+u64 prod_mod(const u64* m, unsigned cnt, unsigned skip, u64 p)
+{
+    u64 x = 1 % p;
+    for (unsigned i = 0; i < cnt; i++)
+        if (i != skip) x = mulmod(x, m[i] % p, p);
+    return x;
+}
+
+void build_consts(EvConsts& c, unsigned n, unsigned r, u64 t, const u64* q, const u64* b)
+{
+    std::memset(&c, 0, sizeof(c));
+    c.r = r;
+    c.n = n;
+    c.t = t;
+    const u64 msk = b[r];
+    for (unsigned i = 0; i < r; i++) c.q[i] = ev_prime(q[i]);
+    for (unsigned j = 0; j <= r; j++) c.b[j] = ev_prime(b[j]);
+    const u64 mt = 1ull << 32, mask = mt - 1;
+    u64 q_mt = 1;
+    for (unsigned i = 0; i < r; i++) q_mt *= q[i];
+    c.ext_neg_qinv_mt = (mt - inv_mod_2_32(q_mt & mask)) & mask;
+    for (unsigned i = 0; i < r; i++) {
+        const u64 punct = prod_mod(q, r, i, q[i]);
+        const u64 pinv = modinv(punct, q[i]);
+        c.ext_qc[i] = mulmod(mt % q[i], pinv, q[i]);
+        c.ext_qcp[i] = shoup(c.ext_qc[i], q[i]);
+        c.rs_qc[i] = mulmod(t % q[i], pinv, q[i]);
+        c.rs_qcp[i] = shoup(c.rs_qc[i], q[i]);
+        u64 pm = 1;
+        for (unsigned k = 0; k < r; k++)
+            if (k != i) pm *= q[k];
+        c.ext_mt[i] = pm & mask;
+    }
+    for (unsigned j = 0; j <= r; j++) {
+        const u64 bj = b[j];
+        const u64 mt_inv = modinv(mt % bj, bj);
+        for (unsigned i = 0; i < r; i++) {
+            c.ext_w[i][j] = mulmod(prod_mod(q, r, i, bj), mt_inv, bj);
+            c.rs_w[i][j] = bj - modinv(q[i] % bj, bj);
+        }
+        const u64 qb = prod_mod(q, r, r, bj);
+        c.ext_qm[j] = mulmod(qb, mt_inv, bj);
+        c.ext_neg_qm[j] = c.ext_qm[j] ? bj - c.ext_qm[j] : 0;
+        c.rs_tq[j] = mulmod(t % bj, modinv(qb, bj), bj);
+    }
+    for (unsigned j = 0; j < r; j++) {
+        c.sk_bc[j] = modinv(prod_mod(b, r, j, b[j]), b[j]);
+        c.sk_bcp[j] = shoup(c.sk_bc[j], b[j]);
+        c.sk_msk_w[j] = modinv(b[j] % msk, msk);
+        for (unsigned i = 0; i < r; i++) c.sk_w[j][i] = prod_mod(b, r, j, q[i]);
+    }
+    c.sk_neg_binv = msk - modinv(prod_mod(b, r, r, msk), msk);
+    for (unsigned i = 0; i < r; i++) {
+        c.sk_bq[i] = prod_mod(b, r, r, q[i]);
+        c.sk_neg_bq[i] = c.sk_bq[i] ? q[i] - c.sk_bq[i] : 0;
+    }
+}
+
+// words of scratch per ciphertext (in units of n): the multiplication's XQ + XB, the relinearization's digits + products
+size_t mult_polys(unsigned r) { return 4 * (2 * (size_t)r + 1); }
+size_t relin_polys(unsigned r) { return (size_t)r * r + 2 * (size_t)r; }
+
+// The keystream key of relinearization keys: NOT keygen_rns's (32 x 0x01).  With keygen's key, relin_keygen_rns and keygen_rns called
+// with the same nonce would draw key 0's uniform and error samples from keygen's bytes, and rlk_0[0] - pk[0] would be s^2 mod q_0.
+const unsigned char kRelinKey[32] = {2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2};
+
+}  // namespace
+
+struct mi355ntt_bfv_eval {
+    const mi355ntt_bfv* bfv = nullptr;
+    mi355ntt_ctx* ctx_q = nullptr;      // exact transforms over Q = q_0 .. q_{r-1}
+    mi355ntt_ctx* ctx_b = nullptr;      // exact transforms over B_sk = b_0 .. b_{r-1}, m_sk
+    int device = 0;
+    unsigned n = 0, r = 0, R = 0;
+    EvConsts h;
+    EvConsts* d = nullptr;
+};
+
+#define EV_HIP(expr)                          \
+    do {                                      \
+        hipError_t e__ = (expr);              \
+        if (e__ != hipSuccess) {              \
+            record_hip_error((int)e__);       \
+            return MI355NTT_EHIP;             \
+        }                                     \
+    } while (0)
+#define EV_RC(expr)             \
+    do {                        \
+        int rc__ = (expr);      \
+        if (rc__) return rc__;  \
+    } while (0)
+
+namespace {
+
+// the checks every batched evaluator call makes before it touches memory
+int ev_count_ok(unsigned count)
+{
+    if (count == 0) return MI355NTT_EINVAL;
+    if (count > kEvalMaxCount) return MI355NTT_EUNSUPPORTED;
+    return MI355NTT_OK;
+}
+
+int ev_multiply(const mi355ntt_bfv_eval* ev, u64* c3, const u64* a, const u64* b, unsigned count, u64* scratch, hipStream_t s)
+{
+    const unsigned r = ev->r;
+    const size_t nq = (size_t)count * r, nb = (size_t)count * (r + 1);
+    u64* xq = scratch;
+    u64* xb = scratch + 4 * nq * ev->n;
+    EV_HIP(ev_extend(ev->h, ev->d, xq, xb, a, b, count, s));
+    EV_RC(mi355ntt_forward_batch(ev->ctx_q, xq, (unsigned)(4 * nq), r, s));
+    EV_RC(mi355ntt_forward_batch(ev->ctx_b, xb, (unsigned)(4 * nb), r + 1, s));
+    EV_HIP(ev_tensor(ev->h, ev->d, xq, xb, count, s));
+    EV_RC(mi355ntt_inverse_batch(ev->ctx_q, xq, (unsigned)(3 * nq), r, s));
+    EV_RC(mi355ntt_inverse_batch(ev->ctx_b, xb, (unsigned)(3 * nb), r + 1, s));
+    EV_HIP(ev_rescale(ev->h, ev->d, c3, xq, xb, count, s));
+    return MI355NTT_OK;
+}
+
+int ev_relinearize(const mi355ntt_bfv_eval* ev, u64* c, const u64* c3, const u64* rlk, unsigned count, u64* scratch, hipStream_t s)
+{
+    const unsigned r = ev->r, R = ev->R, n = ev->n;
+    u64* D = scratch;
+    u64* P = scratch + (size_t)count * r * r * n;
+    EV_HIP(ev_digits(ev->h, ev->d, D, c3, count, s));
+    EV_RC(mi355ntt_forward_batch(ev->ctx_q, D, count * r * r, r, s));
+    EV_HIP(ev_relin_dot(ev->h, ev->d, P, D, rlk, count, s));
+    EV_RC(mi355ntt_inverse_batch(ev->ctx_q, P, 2 * count * r, r, s));
+    const size_t cs = (size_t)count * R * n;
+    EV_HIP(ev_addsub(ev->h, ev->d, EvView{c, cs, (size_t)R * n}, EvView{const_cast<u64*>(c3), cs, (size_t)R * n},
+                     EvView{P, (size_t)count * r * n, (size_t)r * n}, 2, count, false, s));
+    return MI355NTT_OK;
+}
+
+// rlk slot 0 of every key holds e_i (coefficient domain), slot 1 a_i: finish -(a_i s + e_i) + s^2 g_i in the NTT domain
+int ev_finish_rlk(const mi355ntt_bfv_eval* ev, u64* rlk, const u64* sk, hipStream_t s)
+{
+    for (unsigned i = 0; i < ev->r; i++) EV_RC(mi355ntt_forward_batch(ev->ctx_q, rlk + (size_t)i * 2 * ev->R * ev->n, ev->r, ev->r, s));
+    EV_HIP(ev_relin_key(ev->h, ev->d, rlk, sk, s));
+    return MI355NTT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi355ntt_bfv_aux_primes(unsigned n, unsigned r, mi355ntt_u64* b, mi355ntt_u64* psi_b)
+{
+    if (!b) return MI355NTT_EINVAL;
+    return aux_primes(n, r, nullptr, 0, b, psi_b);
+}
+
+int mi355ntt_bfv_eval_create(mi355ntt_bfv_eval** out, const mi355ntt_bfv* bfv)
+{
+    if (!out || !bfv) return MI355NTT_EINVAL;
+    *out = nullptr;
+    const BfvParams& p = bfv->p;
+    const unsigned R = p.R, r = p.r, n = p.n;
+    if (r < 1 || r > kEvalMaxQ) return MI355NTT_EUNSUPPORTED;
+    u64 q[kMaxPrimes], psi[kMaxPrimes], b[kEvalMaxBsk], psi_b[kEvalMaxBsk];
+    for (unsigned i = 0; i < R; i++) {
+        EV_RC(mi355ntt_ctx_prime(bfv->ntt, i, &q[i], nullptr, nullptr, &psi[i], nullptr));
+        if (i < r && q[i] >= (1ull << 61)) return MI355NTT_EUNSUPPORTED;     // 128-bit sums of r + 2 products (bfv_eval.hpp)
+    }
+    EV_RC(aux_primes(n, r, q, R, b, psi_b));
+    // BEHZ size condition: 4 n t Q + 2 (r + 1) B < B m_sk, checked as
+    // sum bits(q_i) + log2 n + log2 t + 3 <= sum (bits(b_j) - 1)
+    unsigned lhs = 3, rhs = 0, lg = 0;
+    while ((1u << lg) < n) lg++;
+    lhs += lg + bit_length(p.t) - 1;
+    for (unsigned i = 0; i < r; i++) lhs += bit_length(q[i]);
+    for (unsigned j = 0; j <= r; j++) rhs += bit_length(b[j]) - 1;
+    if (lhs > rhs) return MI355NTT_EUNSUPPORTED;
+    mi355ntt_bfv_eval* ev = new (std::nothrow) mi355ntt_bfv_eval();
+    if (!ev) return MI355NTT_ENOMEM;
+    ev->bfv = bfv;
+    ev->device = mi355ntt_ctx_device(bfv->ntt);
+    ev->n = n;
+    ev->r = r;
+    ev->R = R;
+    build_consts(ev->h, n, r, p.t, q, b);
+    int rc = mi355ntt_ctx_create_ex(&ev->ctx_q, n, r, q, psi, ev->device, MI355NTT_CTX_EXACT_ON_INEXACT_PRIMES);
+    if (!rc) rc = mi355ntt_ctx_create_ex(&ev->ctx_b, n, r + 1, b, psi_b, ev->device, MI355NTT_CTX_EXACT_ON_INEXACT_PRIMES);
+    if (!rc) {
+        DeviceScope scope(ev->device);
+        hipError_t e = scope.err;
+        if (e == hipSuccess) e = hipMalloc(&ev->d, sizeof(EvConsts));
+        if (e == hipSuccess) e = hipMemcpy(ev->d, &ev->h, sizeof(EvConsts), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            record_hip_error((int)e);
+            rc = e == hipErrorOutOfMemory ? MI355NTT_ENOMEM : MI355NTT_EHIP;
+        }
+    }
+    if (rc) {
+        mi355ntt_bfv_eval_destroy(ev);
+        return rc;
+    }
+    *out = ev;
+    return MI355NTT_OK;
+}
+
+int mi355ntt_bfv_eval_destroy(mi355ntt_bfv_eval* ev)
+{
+    if (!ev) return MI355NTT_OK;
+    {
+        DeviceScope scope(ev->device);
+        if (ev->d) (void)hipFree(ev->d);
+    }
+    if (ev->ctx_q) mi355ntt_ctx_destroy(ev->ctx_q);
+    if (ev->ctx_b) mi355ntt_ctx_destroy(ev->ctx_b);
+    delete ev;
+    return MI355NTT_OK;
+}
+
+int mi355ntt_bfv_eval_aux_primes(const mi355ntt_bfv_eval* ev, mi355ntt_u64* b)
+{
+    if (!ev || !b) return MI355NTT_EINVAL;
+    for (unsigned j = 0; j <= ev->r; j++) b[j] = ev->h.b[j].q;
+    return MI355NTT_OK;
+}
+
+size_t mi355ntt_bfv_eval_scratch_bytes(const mi355ntt_bfv_eval* ev, unsigned count)
+{
+    if (!ev) return 0;
+    const size_t m = mult_polys(ev->r), rl = relin_polys(ev->r);
+    return ((m > rl ? m : rl) + 3 * (size_t)ev->R) * count * ev->n * sizeof(u64);
+}
+
+int mi355ntt_bfv_relin_keygen(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_rlk, const mi355ntt_u64* d_secret_key, const mi355ntt_u64* d_a,
+                              const mi355ntt_u64* d_e, mi355ntt_stream stream)
+{
+    if (!ev || !d_rlk || !d_secret_key || !d_a || !d_e) return MI355NTT_EINVAL;
+    const unsigned r = ev->r, R = ev->R, n = ev->n;
+    hipStream_t s = (hipStream_t)stream;
+    DeviceScope scope(ev->device);
+    EV_HIP(scope.err);
+    const size_t words = (size_t)r * n * sizeof(u64);
+    for (unsigned i = 0; i < r; i++) {
+        u64* k0 = d_rlk + (size_t)i * 2 * R * n;
+        EV_HIP(hipMemcpyAsync(k0, d_e + (size_t)i * R * n, words, hipMemcpyDeviceToDevice, s));
+        EV_HIP(hipMemcpyAsync(k0 + (size_t)R * n, d_a + (size_t)i * R * n, words, hipMemcpyDeviceToDevice, s));
+    }
+    return ev_finish_rlk(ev, d_rlk, d_secret_key, s);
+}
+
+int mi355ntt_bfv_relin_keygen_rns(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_rlk, const mi355ntt_u64* d_secret_key, void* d_in,
+                                  mi355ntt_u64* d_temp, mi355ntt_u64 nonce, mi355ntt_stream stream)
+{
+    if (!ev || !d_rlk || !d_secret_key || !d_in || !d_temp) return MI355NTT_EINVAL;
+    if (((uintptr_t)d_in & 15) != 0) return MI355NTT_EINVAL;
+    const unsigned r = ev->r, R = ev->R, n = ev->n;
+    const size_t bytes = mi355ntt_bfv_keygen_random_bytes(ev->bfv);
+    DeviceScope scope(ev->device);
+    EV_HIP(scope.err);
+    EV_RC(mi355ntt_salsa20_keystream(d_in, r * bytes, kRelinKey, nonce, stream));
+    for (unsigned i = 0; i < r; i++) {
+        /* keygen's conversions: the uniform sample lands in slot 1 (the public key's second half), the Gaussian one in slot 0; the
+         * ternary one in d_temp is not used */
+        u64* k0 = d_rlk + (size_t)i * 2 * R * n;
+        EV_RC(mi355ntt_bfv_sample_keygen(ev->bfv, static_cast<unsigned char*>(d_in) + i * bytes, d_temp, k0, k0, stream));
+    }
+    return ev_finish_rlk(ev, d_rlk, d_secret_key, (hipStream_t)stream);
+}
+
+static int ev_addsub_call(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_b, unsigned count,
+                          mi355ntt_stream stream, bool sub)
+{
+    if (!ev || !d_c || !d_a || !d_b) return MI355NTT_EINVAL;
+    EV_RC(ev_count_ok(count));
+    DeviceScope scope(ev->device);
+    EV_HIP(scope.err);
+    const size_t cs = (size_t)count * ev->R * ev->n, zs = (size_t)ev->R * ev->n;
+    EV_HIP(ev_addsub(ev->h, ev->d, EvView{d_c, cs, zs}, EvView{const_cast<u64*>(d_a), cs, zs}, EvView{const_cast<u64*>(d_b), cs, zs}, 2,
+                     count, sub, (hipStream_t)stream));
+    return MI355NTT_OK;
+}
+
+int mi355ntt_bfv_add(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_b, unsigned count,
+                     mi355ntt_stream stream)
+{
+    return ev_addsub_call(ev, d_c, d_a, d_b, count, stream, false);
+}
+
+int mi355ntt_bfv_sub(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_b, unsigned count,
+                     mi355ntt_stream stream)
+{
+    return ev_addsub_call(ev, d_c, d_a, d_b, count, stream, true);
+}
+
+int mi355ntt_bfv_multiply(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c3, const mi355ntt_u64* d_a, const mi355ntt_u64* d_b,
+                          unsigned count, void* d_scratch, mi355ntt_stream stream)
+{
+    if (!ev || !d_c3 || !d_a || !d_b || !d_scratch) return MI355NTT_EINVAL;
+    EV_RC(ev_count_ok(count));
+    DeviceScope scope(ev->device);
+    EV_HIP(scope.err);
+    return ev_multiply(ev, d_c3, d_a, d_b, count, static_cast<u64*>(d_scratch), (hipStream_t)stream);
+}
+
+int mi355ntt_bfv_relinearize(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_c3, const mi355ntt_u64* d_rlk,
+                             unsigned count, void* d_scratch, mi355ntt_stream stream)
+{
+    if (!ev || !d_c || !d_c3 || !d_rlk || !d_scratch) return MI355NTT_EINVAL;
+    EV_RC(ev_count_ok(count));
+    DeviceScope scope(ev->device);
+    EV_HIP(scope.err);
+    return ev_relinearize(ev, d_c, d_c3, d_rlk, count, static_cast<u64*>(d_scratch), (hipStream_t)stream);
+}
+
+int mi355ntt_bfv_multiply_relin(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_b,
+                                const mi355ntt_u64* d_rlk, unsigned count, void* d_scratch, mi355ntt_stream stream)
+{
+    if (!ev || !d_c || !d_a || !d_b || !d_rlk || !d_scratch) return MI355NTT_EINVAL;
+    EV_RC(ev_count_ok(count));
+    DeviceScope scope(ev->device);
+    EV_HIP(scope.err);
+    const size_t m = mult_polys(ev->r), rl = relin_polys(ev->r);
+    u64* work = static_cast<u64*>(d_scratch);
+    u64* c3 = work + (m > rl ? m : rl) * count * ev->n;
+    EV_RC(ev_multiply(ev, c3, d_a, d_b, count, work, (hipStream_t)stream));
+    return ev_relinearize(ev, d_c, c3, d_rlk, count, work, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -90,16 +90,6 @@ namespace mi355ntt {
 void record_hip_error(int e);      // capi.cpp: what mi355ntt_last_hip_error() reports
 }
 
-struct mi355ntt_bfv {
-    mi355ntt_ctx* ntt = nullptr;
-    BfvParams p;
-    BfvDevice d;
-    void* d_prime = nullptr;
-    void* d_bcm = nullptr;
-    void* d_epi = nullptr;        // [R] BfvEpiPrime: the epilogue constants of the batched decryption
-    bool epi_ok = false;          // the one-product form of the scaling is the reference's words for these moduli
-};
-
 #define BFV_HIP(expr)                         \
     do {                                      \
         hipError_t e__ = (expr);              \

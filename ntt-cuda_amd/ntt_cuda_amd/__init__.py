@@ -81,6 +81,18 @@ _SIGNATURES = {
     "mi355ntt_polymul_batch_shared": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, vp]),
     "mi355ntt_bfv_encrypt_batch": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_uint, vp]),
     "mi355ntt_bfv_decrypt_batch": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint, vp]),
+    "mi355ntt_bfv_aux_primes": (ctypes.c_int, [ctypes.c_uint, ctypes.c_uint, u64p, u64p]),
+    "mi355ntt_bfv_eval_create": (ctypes.c_int, [ctypes.POINTER(vp), vp]),
+    "mi355ntt_bfv_eval_destroy": (ctypes.c_int, [vp]),
+    "mi355ntt_bfv_eval_aux_primes": (ctypes.c_int, [vp, u64p]),
+    "mi355ntt_bfv_eval_scratch_bytes": (ctypes.c_size_t, [vp, ctypes.c_uint]),
+    "mi355ntt_bfv_relin_keygen": (ctypes.c_int, [vp, vp, vp, vp, vp, vp]),
+    "mi355ntt_bfv_relin_keygen_rns": (ctypes.c_int, [vp, vp, vp, vp, vp, u64, vp]),
+    "mi355ntt_bfv_add": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_uint, vp]),
+    "mi355ntt_bfv_sub": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_uint, vp]),
+    "mi355ntt_bfv_multiply": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_uint, vp, vp]),
+    "mi355ntt_bfv_relinearize": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_uint, vp, vp]),
+    "mi355ntt_bfv_multiply_relin": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_uint, vp, vp]),
     "mi355ntt_shard_range": (ctypes.c_int, [ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, u32p, u32p]),
     "mi355ntt_shards_create": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.c_uint, ctypes.c_uint]),
     "mi355ntt_shards_destroy": (ctypes.c_int, [vp]),

@@ -143,3 +143,127 @@ class BFVContext:
         from . import lib, _check, _ptr, _byte_ptr, _stream
         _check(lib().mi355ntt_bfv_encryption_rns(self._h, _ptr(c), _ptr(public_key), _byte_ptr(rnd), _ptr(e), _ptr(m), int(nonce),
                                                  _stream(stream)), "mi355ntt_bfv_encryption_rns")
+
+
+def aux_primes(n, r):
+    """mi355ntt_bfv_aux_primes (host only): the r + 1 primes of B_sk for ring degree n, m_sk last, and a primitive 2n-th root of each"""
+    import numpy as np
+    from . import lib, _check, u64p
+    b, psi = np.zeros(r + 1, np.uint64), np.zeros(r + 1, np.uint64)
+    _check(lib().mi355ntt_bfv_aux_primes(int(n), int(r), b.ctypes.data_as(u64p), psi.ctypes.data_as(u64p)), "mi355ntt_bfv_aux_primes")
+    return [int(x) for x in b], [int(x) for x in psi]
+
+
+class BFVEvaluator:
+    """Homomorphic evaluation on the ciphertexts of a BFVContext (C ABI section "BFV evaluation"): add, sub, multiply (BEHZ tensor
+    product and t/Q rescale), relinearize and both fused.  Ciphertexts are [2][count][num_primes][n] as encrypt_batch writes them
+    (count = 1: [2][num_primes][n]); the product before relinearization is [3][count][num_primes][n]; the relinearization key is
+    [r][2][num_primes][n], r = num_primes - 1.  Scratch is allocated per call from torch's caching allocator, on the launch stream,
+    unless passed; a caller-owned scratch buffer must not be shared by calls that may run concurrently."""
+
+    def __init__(self, bfv):
+        import ctypes
+        from . import lib, _check, vp
+        self._h = vp()
+        _check(lib().mi355ntt_bfv_eval_create(ctypes.byref(self._h), bfv._h), "mi355ntt_bfv_eval_create")
+        self.bfv = bfv                      # the C object keeps a pointer to it
+        self.n, self.num_primes, self.device = bfv.n, bfv.num_primes, bfv.device
+        self.r = self.num_primes - 1
+
+    def close(self):
+        from . import lib, vp
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().mi355ntt_bfv_eval_destroy(self._h)
+            self._h = vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def aux_primes(self):
+        import numpy as np
+        from . import lib, _check, u64p
+        b = np.zeros(self.r + 1, np.uint64)
+        _check(lib().mi355ntt_bfv_eval_aux_primes(self._h, b.ctypes.data_as(u64p)), "mi355ntt_bfv_eval_aux_primes")
+        return [int(x) for x in b]
+
+    def scratch_bytes(self, count=1):
+        from . import lib
+        return int(lib().mi355ntt_bfv_eval_scratch_bytes(self._h, int(count)))
+
+    def scratch(self, count=1):
+        """a device buffer large enough for calls with `count` ciphertexts"""
+        import torch
+        return torch.empty(max(1, self.scratch_bytes(count) // 8), dtype=torch.int64, device="cuda:%d" % self.device)
+
+    def _p(self, t, polys):
+        from . import _ptr_n
+        return _ptr_n(t, int(polys) * self.n, self.device)
+
+    def _launch(self, fn, count, scratch, stream):
+        """fn(scratch pointer, stream handle).  Without `scratch` the buffer comes from torch's caching allocator ON THE LAUNCH STREAM
+        and lives until the call is enqueued: freed afterwards, it returns to that stream's pool, where only work ordered after
+        the call's kernels can receive it (a buffer taken on another stream could be handed out again while they still run)."""
+        import torch
+        from . import _stream
+        polys = self.scratch_bytes(count) // 8 // self.n
+        if scratch is not None:
+            return fn(self._p(scratch, polys), _stream(stream))
+        s = torch.cuda.current_stream() if stream is None else stream
+        if isinstance(s, int):
+            s = torch.cuda.ExternalStream(s, device="cuda:%d" % self.device)
+        with torch.cuda.stream(s):
+            buf = self.scratch(count)
+        fn(self._p(buf, polys), _stream(s))
+        del buf
+
+    def relin_keygen(self, rlk, secret_key, a, e, stream=None):
+        from . import lib, _check, _stream
+        R, r = self.num_primes, self.r
+        _check(lib().mi355ntt_bfv_relin_keygen(self._h, self._p(rlk, 2 * r * R), self._p(secret_key, R), self._p(a, r * R), self._p(e, r * R),
+                                               _stream(stream)), "mi355ntt_bfv_relin_keygen")
+
+    @property
+    def relin_random_bytes(self):
+        return self.r * self.bfv.keygen_random_bytes
+
+    def relin_keygen_rns(self, rlk, secret_key, rnd, temp, nonce, stream=None):
+        """the complete relinearization key generation; `nonce` has no default: a fresh one per key"""
+        from . import lib, _check, _byte_ptr, _stream
+        R, r = self.num_primes, self.r
+        assert rnd.numel() >= self.relin_random_bytes
+        _check(lib().mi355ntt_bfv_relin_keygen_rns(self._h, self._p(rlk, 2 * r * R), self._p(secret_key, R), _byte_ptr(rnd), self._p(temp, R),
+                                                   int(nonce), _stream(stream)), "mi355ntt_bfv_relin_keygen_rns")
+
+    def add(self, c, a, b, count=1, stream=None):
+        from . import lib, _check, _stream
+        w = 2 * count * self.num_primes
+        _check(lib().mi355ntt_bfv_add(self._h, self._p(c, w), self._p(a, w), self._p(b, w), int(count), _stream(stream)), "mi355ntt_bfv_add")
+
+    def sub(self, c, a, b, count=1, stream=None):
+        from . import lib, _check, _stream
+        w = 2 * count * self.num_primes
+        _check(lib().mi355ntt_bfv_sub(self._h, self._p(c, w), self._p(a, w), self._p(b, w), int(count), _stream(stream)), "mi355ntt_bfv_sub")
+
+    def multiply(self, c3, a, b, count=1, scratch=None, stream=None):
+        from . import lib, _check
+        R = self.num_primes
+        args = (self._p(c3, 3 * count * R), self._p(a, 2 * count * R), self._p(b, 2 * count * R), int(count))
+        self._launch(lambda scr, s: _check(lib().mi355ntt_bfv_multiply(self._h, *args, scr, s), "mi355ntt_bfv_multiply"), count, scratch, stream)
+
+    def relinearize(self, c, c3, rlk, count=1, scratch=None, stream=None):
+        from . import lib, _check
+        R = self.num_primes
+        args = (self._p(c, 2 * count * R), self._p(c3, 3 * count * R), self._p(rlk, 2 * self.r * R), int(count))
+        self._launch(lambda scr, s: _check(lib().mi355ntt_bfv_relinearize(self._h, *args, scr, s), "mi355ntt_bfv_relinearize"), count, scratch,
+                     stream)
+
+    def multiply_relin(self, c, a, b, rlk, count=1, scratch=None, stream=None):
+        from . import lib, _check
+        R = self.num_primes
+        args = (self._p(c, 2 * count * R), self._p(a, 2 * count * R), self._p(b, 2 * count * R), self._p(rlk, 2 * self.r * R), int(count))
+        self._launch(lambda scr, s: _check(lib().mi355ntt_bfv_multiply_relin(self._h, *args, scr, s), "mi355ntt_bfv_multiply_relin"), count,
+                     scratch, stream)
