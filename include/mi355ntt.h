@@ -454,6 +454,53 @@ int mi355ntt_bfv_relinearize(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, con
 int mi355ntt_bfv_multiply_relin(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_b,
                                 const mi355ntt_u64* d_rlk, unsigned count, void* d_scratch, mi355ntt_stream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * BFV evaluation with plaintext operands and Galois automorphisms ("Plaintext operands and Galois automorphisms"), on
+ * the same evaluator and under the semantics of the block above; further:
+ *   - A plaintext is [count][n] words; its coefficients are taken mod t (a mask: t is a power of two).
+ *   - Outputs are canonical; d_c may alias the ciphertext input d_a.
+ *   - A Galois element g must be odd with 1 <= g < 2n; any other g gives MI355NTT_EINVAL before any memory is touched.
+ *     tau_g(x^i) = x^(g i mod 2n), an exponent >= n flipping the sign.
+ *   - Scratch is mi355ntt_bfv_eval_scratch_bytes(ev, count), unchanged: per ciphertext apply_galois uses r^2 + 3 r polynomials and
+ *     multiply_plain 3 r (multiply_plain_ntt 2 r), both within its max(8 r + 4, r^2 + 2 r) + 3 num_primes.
+ * Noise (infinity norm of v in c0 + c1 s = Delta m + v mod Q, Delta = floor(Q / t), B_e the error bound of the key's samples):
+ * add_plain / sub_plain |v'| <= |v| + 1; multiply_plain |v'| <= (n t / 2) |v| + n (t - 1) / 2; apply_galois
+ * |v'| <= |v| + 1 + r n max(q_i) B_e.
+ * ---------------------------------------------------------------------------------------------- */
+/* d_c = (c0 +/- E(m), c1), ciphertexts [2][count][num_primes][n], d_m [count][n].  E(m) is encryption's encoding exactly (per prime
+ * m floor(q_i / t) + fix, fix = floor((m + (t + 1) / 2) / t), as mi355ntt_bfv_encrypt adds it): add_plain(encrypt(u, e, 0), m) equals
+ * encrypt(u, e, m) word for word.  E(m) = Delta m + fix mod Q, fix in {0, 1}. */
+int mi355ntt_bfv_add_plain(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_m,
+                           unsigned count, mi355ntt_stream stream);
+int mi355ntt_bfv_sub_plain(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_m,
+                           unsigned count, mi355ntt_stream stream);
+/* d_mhat [count][r][n]: the centred lift m~ of d_m [count][n] (m >= t/2 -> m - t) as residues mod q_i, in the NTT domain of the
+ * evaluator's context over Q: the reusable operand of mi355ntt_bfv_multiply_plain_ntt */
+int mi355ntt_bfv_plain_ntt(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_mhat, const mi355ntt_u64* d_m, unsigned count,
+                           mi355ntt_stream stream);
+/* d_c = (c0 m~, c1 m~) mod (x^n + 1, q_i), ciphertext z times plaintext z of d_m [count][n] */
+int mi355ntt_bfv_multiply_plain(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_m,
+                                unsigned count, void* d_scratch, mi355ntt_stream stream);
+/* the same from mi355ntt_bfv_plain_ntt's output.  shared = 0: d_mhat [count][r][n], one plaintext per ciphertext; shared = 1:
+ * d_mhat [r][n], one plaintext for the whole batch.  Any other `shared` gives MI355NTT_EINVAL. */
+int mi355ntt_bfv_multiply_plain_ntt(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_mhat,
+                                    unsigned count, int shared, void* d_scratch, mi355ntt_stream stream);
+/* Galois key for element g, [r][2][num_primes][n], NTT domain over Q, with the layout and conventions of mi355ntt_bfv_relin_keygen:
+ * gk_i = (-(a_i s + e_i) + tau_g(s) g_i, a_i).  tau_g(s) is taken from the NTT-domain key by a permutation of its slots. */
+int mi355ntt_bfv_galois_keygen(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_gk, const mi355ntt_u64* d_secret_key, unsigned g,
+                               const mi355ntt_u64* d_a, const mi355ntt_u64* d_e, mi355ntt_stream stream);
+/* the complete form for num_g >= 1 elements g[0 .. num_g) (host array): d_gk [num_g][r][2][num_primes][n].  One Salsa20 keystream of
+ * num_g * r * mi355ntt_bfv_keygen_random_bytes(bfv) bytes into d_in (16-byte aligned) under a key of its own, 32 x 0x03 (neither
+ * keygen_rns's 0x01 nor relin_keygen_rns's 0x02, so that no nonce makes a Galois key repeat their samples), element k's keys from
+ * offset k r bytes, then keygen's conversions per key as in mi355ntt_bfv_relin_keygen_rns (d_temp [num_primes][n] discarded).
+ * The caller passes a fresh nonce per call.  Every g is checked before anything is launched.  Writes the special slot of d_gk. */
+int mi355ntt_bfv_galois_keygen_rns(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_gk, const mi355ntt_u64* d_secret_key, const unsigned* g,
+                                   unsigned num_g, void* d_in, mi355ntt_u64* d_temp, mi355ntt_u64 nonce, mi355ntt_stream stream);
+/* d_c = (tau_g(c0), tau_g(c1)) key-switched from tau_g(s) back to s with g's key d_gk [r][2][num_primes][n]: the RNS-digit key switch
+ * of mi355ntt_bfv_relinearize applied to tau_g(c1), added to tau_g(c0) */
+int mi355ntt_bfv_apply_galois(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_gk,
+                              unsigned g, unsigned count, void* d_scratch, mi355ntt_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,4 +70,20 @@ hipError_t ev_addsub(const EvConsts& h, const EvConsts* d, EvView out, EvView x,
 // relin key i: slot 0 (holding NTT(e_i)) <- -(a_i s + NTT(e_i)) + [j == i] s^2, slot 1 = a_i untouched; rlk [r][2][R][n]
 hipError_t ev_relin_key(const EvConsts& h, const EvConsts* d, u64* rlk, const u64* s_hat, hipStream_t s);
 
+// ---- launchers (kernels_bfv_galois.hip): plaintext operands and Galois automorphisms.  A plaintext is [count][n] words taken mod t.
+// out = a with c0 +/- E(m) (encryption's encoding m floor(q_j / t) + fix), c1 copied; canonical, out may alias a
+hipError_t ev_plain_addsub(const EvConsts& h, const EvConsts* d, u64* out, const u64* a, const u64* m, unsigned count, bool sub,
+                           hipStream_t s);
+// mhat [count][r][n] = the centred lift of m (m >= t/2 -> m - t) mod q_j, coefficient domain
+hipError_t ev_plain_lift(const EvConsts& h, const EvConsts* d, u64* mhat, const u64* m, unsigned count, hipStream_t s);
+// canonical copy of the Q slots between a ciphertext batch [2][count][R][n] and dense [2][count][r][n] (to_dense) or back
+hipError_t ev_plain_copy(const EvConsts& h, const EvConsts* d, u64* ct, u64* dense, unsigned count, bool to_dense, hipStream_t s);
+// D [count][r][r][n] = the digits of tau_g(c1) (as ev_digits), T [count][r][n] = tau_g(c0); ginv = g^-1 mod 2n
+hipError_t ev_galois_digits(const EvConsts& h, const EvConsts* d, u64* D, u64* T, const u64* a, unsigned ginv, unsigned count,
+                            hipStream_t s);
+// out [2][count][R][n]: c0 = T + P0, c1 = P1 (P [2][count][r][n] as ev_relin_dot writes it, after the inverse transform)
+hipError_t ev_galois_finish(const EvConsts& h, const EvConsts* d, u64* out, const u64* T, const u64* P, unsigned count, hipStream_t s);
+// galois key i: slot 0 (holding NTT(e_i)) <- -(a_i s + NTT(e_i)) + [j == i] tau_g(s), slot 1 = a_i untouched; gk [r][2][R][n]
+hipError_t ev_galois_key(const EvConsts& h, const EvConsts* d, u64* gk, const u64* s_hat, unsigned g, hipStream_t s);
+
 }  // namespace mi355ntt

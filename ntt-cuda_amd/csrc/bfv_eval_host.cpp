@@ -1,6 +1,6 @@
 // bfv_eval_host.cpp -- the BFV evaluator (C ABI section "BFV evaluation" of include/mi355ntt.h): auxiliary prime search, BEHZ
-// constants, relinearization key generation and the drivers.  Transforms run through the evaluator's two exact contexts (one over
-// Q, one over B_sk); the element-wise RNS steps through kernels_bfv_eval.hip.  DESIGN.md, "BFV evaluation", states the algorithm
+// constants, relinearization and Galois key generation and the drivers.  Transforms run through the evaluator's two exact contexts
+// (one over Q, one over B_sk); the element-wise RNS steps through kernels_bfv_eval.hip and kernels_bfv_galois.hip.  DESIGN.md, "BFV evaluation", states the algorithm
 // and the bounds the constants below rely on.
 #include "../../include/mi355ntt.h"
 
@@ -211,15 +211,24 @@ int ev_multiply(const mi355ntt_bfv_eval* ev, u64* c3, const u64* a, const u64* b
     return MI355NTT_OK;
 }
 
+// the key switch shared by relinearization and the Galois automorphisms: digits D [count][r][r][n] (coefficient domain, written by the
+// caller) -> P [2][count][r][n] = INTT(sum_i NTT(D_i) key_i), key [r][2][R][n]
+int ev_keyswitch(const mi355ntt_bfv_eval* ev, u64* P, u64* D, const u64* key, unsigned count, hipStream_t s)
+{
+    const unsigned r = ev->r;
+    EV_RC(mi355ntt_forward_batch(ev->ctx_q, D, count * r * r, r, s));
+    EV_HIP(ev_relin_dot(ev->h, ev->d, P, D, key, count, s));
+    EV_RC(mi355ntt_inverse_batch(ev->ctx_q, P, 2 * count * r, r, s));
+    return MI355NTT_OK;
+}
+
 int ev_relinearize(const mi355ntt_bfv_eval* ev, u64* c, const u64* c3, const u64* rlk, unsigned count, u64* scratch, hipStream_t s)
 {
     const unsigned r = ev->r, R = ev->R, n = ev->n;
     u64* D = scratch;
     u64* P = scratch + (size_t)count * r * r * n;
     EV_HIP(ev_digits(ev->h, ev->d, D, c3, count, s));
-    EV_RC(mi355ntt_forward_batch(ev->ctx_q, D, count * r * r, r, s));
-    EV_HIP(ev_relin_dot(ev->h, ev->d, P, D, rlk, count, s));
-    EV_RC(mi355ntt_inverse_batch(ev->ctx_q, P, 2 * count * r, r, s));
+    EV_RC(ev_keyswitch(ev, P, D, rlk, count, s));
     const size_t cs = (size_t)count * R * n;
     EV_HIP(ev_addsub(ev->h, ev->d, EvView{c, cs, (size_t)R * n}, EvView{const_cast<u64*>(c3), cs, (size_t)R * n},
                      EvView{P, (size_t)count * r * n, (size_t)r * n}, 2, count, false, s));
@@ -233,6 +242,31 @@ int ev_finish_rlk(const mi355ntt_bfv_eval* ev, u64* rlk, const u64* sk, hipStrea
     EV_HIP(ev_relin_key(ev->h, ev->d, rlk, sk, s));
     return MI355NTT_OK;
 }
+
+// the r keys' e_i (slot 0, coefficient domain) to the NTT domain, then -(a_i s + e_i) + tau_g(s) g_i
+int ev_finish_gk(const mi355ntt_bfv_eval* ev, u64* gk, const u64* sk, unsigned g, hipStream_t s)
+{
+    for (unsigned i = 0; i < ev->r; i++) EV_RC(mi355ntt_forward_batch(ev->ctx_q, gk + (size_t)i * 2 * ev->R * ev->n, ev->r, ev->r, s));
+    EV_HIP(ev_galois_key(ev->h, ev->d, gk, sk, g, s));
+    return MI355NTT_OK;
+}
+
+// a Galois element: odd, 1 <= g < 2n
+bool ev_galois_ok(const mi355ntt_bfv_eval* ev, unsigned g) { return (g & 1) && g < 2 * ev->n; }
+
+// g^-1 mod 2n for odd g (Newton over 2^32; 2n divides 2^32)
+unsigned ev_galois_inverse(unsigned g, unsigned n)
+{
+    unsigned x = g;
+    for (int i = 0; i < 5; i++) x *= 2 - g * x;
+    return x & (2 * n - 1);
+}
+
+// Scratch polynomials per ciphertext: apply_galois r^2 + 3 r (digits, products, the staged tau_g(c0)), multiply_plain 3 r (the dense
+// copies and the lifted plaintext).  Both fit in mi355ntt_bfv_eval_scratch_bytes's max(8 r + 4, r^2 + 2 r) + 3 (r + 1).
+
+// The keystream key of Galois keys: neither keygen_rns's (32 x 0x01) nor relinearization's (32 x 0x02), for the reason kRelinKey gives.
+const unsigned char kGaloisKey[32] = {3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3};
 
 }  // namespace
 
@@ -413,6 +447,151 @@ int mi355ntt_bfv_multiply_relin(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, 
     u64* c3 = work + (m > rl ? m : rl) * count * ev->n;
     EV_RC(ev_multiply(ev, c3, d_a, d_b, count, work, (hipStream_t)stream));
     return ev_relinearize(ev, d_c, c3, d_rlk, count, work, (hipStream_t)stream);
+}
+
+static int ev_plain_addsub_call(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_m,
+                                unsigned count, mi355ntt_stream stream, bool sub)
+{
+    if (!ev || !d_c || !d_a || !d_m) return MI355NTT_EINVAL;
+    EV_RC(ev_count_ok(count));
+    DeviceScope scope(ev->device);
+    EV_HIP(scope.err);
+    EV_HIP(ev_plain_addsub(ev->h, ev->d, d_c, d_a, d_m, count, sub, (hipStream_t)stream));
+    return MI355NTT_OK;
+}
+
+int mi355ntt_bfv_add_plain(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_m,
+                           unsigned count, mi355ntt_stream stream)
+{
+    return ev_plain_addsub_call(ev, d_c, d_a, d_m, count, stream, false);
+}
+
+int mi355ntt_bfv_sub_plain(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_m,
+                           unsigned count, mi355ntt_stream stream)
+{
+    return ev_plain_addsub_call(ev, d_c, d_a, d_m, count, stream, true);
+}
+
+int mi355ntt_bfv_plain_ntt(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_mhat, const mi355ntt_u64* d_m, unsigned count,
+                           mi355ntt_stream stream)
+{
+    if (!ev || !d_mhat || !d_m) return MI355NTT_EINVAL;
+    EV_RC(ev_count_ok(count));
+    DeviceScope scope(ev->device);
+    EV_HIP(scope.err);
+    hipStream_t s = (hipStream_t)stream;
+    EV_HIP(ev_plain_lift(ev->h, ev->d, d_mhat, d_m, count, s));
+    EV_RC(mi355ntt_forward_batch(ev->ctx_q, d_mhat, count * ev->r, ev->r, s));
+    return MI355NTT_OK;
+}
+
+namespace {
+
+// c_h mhat for both components: canonical dense copies X [2][count][r][n] in scratch, fused products, write-back
+int ev_multiply_plain(const mi355ntt_bfv_eval* ev, u64* c, const u64* a, const u64* mhat, unsigned count, bool shared, u64* X,
+                      hipStream_t s)
+{
+    const unsigned r = ev->r;
+    const unsigned half = count * r;
+    EV_HIP(ev_plain_copy(ev->h, ev->d, const_cast<u64*>(a), X, count, true, s));
+    if (shared) {
+        EV_RC(mi355ntt_polymul_batch_shared(ev->ctx_q, X, mhat, 2 * half, r, 0, s));
+    } else {
+        EV_RC(mi355ntt_polymul_batch(ev->ctx_q, X, mhat, half, r, s));
+        EV_RC(mi355ntt_polymul_batch(ev->ctx_q, X + (size_t)half * ev->n, mhat, half, r, s));
+    }
+    EV_HIP(ev_plain_copy(ev->h, ev->d, c, X, count, false, s));
+    return MI355NTT_OK;
+}
+
+}  // namespace
+
+int mi355ntt_bfv_multiply_plain(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_m,
+                                unsigned count, void* d_scratch, mi355ntt_stream stream)
+{
+    if (!ev || !d_c || !d_a || !d_m || !d_scratch) return MI355NTT_EINVAL;
+    EV_RC(ev_count_ok(count));
+    DeviceScope scope(ev->device);
+    EV_HIP(scope.err);
+    hipStream_t s = (hipStream_t)stream;
+    u64* X = static_cast<u64*>(d_scratch);
+    u64* mhat = X + (size_t)2 * count * ev->r * ev->n;
+    EV_HIP(ev_plain_lift(ev->h, ev->d, mhat, d_m, count, s));
+    EV_RC(mi355ntt_forward_batch(ev->ctx_q, mhat, count * ev->r, ev->r, s));
+    return ev_multiply_plain(ev, d_c, d_a, mhat, count, false, X, s);
+}
+
+int mi355ntt_bfv_multiply_plain_ntt(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_mhat,
+                                    unsigned count, int shared, void* d_scratch, mi355ntt_stream stream)
+{
+    if (!ev || !d_c || !d_a || !d_mhat || !d_scratch) return MI355NTT_EINVAL;
+    if (shared != 0 && shared != 1) return MI355NTT_EINVAL;
+    EV_RC(ev_count_ok(count));
+    DeviceScope scope(ev->device);
+    EV_HIP(scope.err);
+    return ev_multiply_plain(ev, d_c, d_a, d_mhat, count, shared == 1, static_cast<u64*>(d_scratch), (hipStream_t)stream);
+}
+
+int mi355ntt_bfv_galois_keygen(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_gk, const mi355ntt_u64* d_secret_key, unsigned g,
+                               const mi355ntt_u64* d_a, const mi355ntt_u64* d_e, mi355ntt_stream stream)
+{
+    if (!ev || !d_gk || !d_secret_key || !d_a || !d_e) return MI355NTT_EINVAL;
+    if (!ev_galois_ok(ev, g)) return MI355NTT_EINVAL;
+    const unsigned r = ev->r, R = ev->R, n = ev->n;
+    hipStream_t s = (hipStream_t)stream;
+    DeviceScope scope(ev->device);
+    EV_HIP(scope.err);
+    const size_t words = (size_t)r * n * sizeof(u64);
+    for (unsigned i = 0; i < r; i++) {
+        u64* k0 = d_gk + (size_t)i * 2 * R * n;
+        EV_HIP(hipMemcpyAsync(k0, d_e + (size_t)i * R * n, words, hipMemcpyDeviceToDevice, s));
+        EV_HIP(hipMemcpyAsync(k0 + (size_t)R * n, d_a + (size_t)i * R * n, words, hipMemcpyDeviceToDevice, s));
+    }
+    return ev_finish_gk(ev, d_gk, d_secret_key, g, s);
+}
+
+int mi355ntt_bfv_galois_keygen_rns(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_gk, const mi355ntt_u64* d_secret_key, const unsigned* g,
+                                   unsigned num_g, void* d_in, mi355ntt_u64* d_temp, mi355ntt_u64 nonce, mi355ntt_stream stream)
+{
+    if (!ev || !d_gk || !d_secret_key || !g || !d_in || !d_temp || num_g == 0) return MI355NTT_EINVAL;
+    if (((uintptr_t)d_in & 15) != 0) return MI355NTT_EINVAL;
+    for (unsigned k = 0; k < num_g; k++)
+        if (!ev_galois_ok(ev, g[k])) return MI355NTT_EINVAL;
+    const unsigned r = ev->r, R = ev->R, n = ev->n;
+    const size_t bytes = mi355ntt_bfv_keygen_random_bytes(ev->bfv);
+    DeviceScope scope(ev->device);
+    EV_HIP(scope.err);
+    EV_RC(mi355ntt_salsa20_keystream(d_in, (size_t)num_g * r * bytes, kGaloisKey, nonce, stream));
+    for (unsigned k = 0; k < num_g; k++) {
+        u64* gk = d_gk + (size_t)k * r * 2 * R * n;
+        for (unsigned i = 0; i < r; i++) {
+            /* as relin_keygen_rns: uniform sample into slot 1, Gaussian into slot 0, the ternary one into d_temp (discarded) */
+            u64* k0 = gk + (size_t)i * 2 * R * n;
+            EV_RC(mi355ntt_bfv_sample_keygen(ev->bfv, static_cast<unsigned char*>(d_in) + ((size_t)k * r + i) * bytes, d_temp, k0, k0,
+                                             stream));
+        }
+        EV_RC(ev_finish_gk(ev, gk, d_secret_key, g[k], (hipStream_t)stream));
+    }
+    return MI355NTT_OK;
+}
+
+int mi355ntt_bfv_apply_galois(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_gk,
+                              unsigned g, unsigned count, void* d_scratch, mi355ntt_stream stream)
+{
+    if (!ev || !d_c || !d_a || !d_gk || !d_scratch) return MI355NTT_EINVAL;
+    if (!ev_galois_ok(ev, g)) return MI355NTT_EINVAL;
+    EV_RC(ev_count_ok(count));
+    DeviceScope scope(ev->device);
+    EV_HIP(scope.err);
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned r = ev->r, n = ev->n;
+    u64* D = static_cast<u64*>(d_scratch);                       // [count][r][r][n]
+    u64* P = D + (size_t)count * r * r * n;                      // [2][count][r][n]
+    u64* T = P + (size_t)2 * count * r * n;                      // [count][r][n]
+    EV_HIP(ev_galois_digits(ev->h, ev->d, D, T, d_a, ev_galois_inverse(g, n), count, s));
+    EV_RC(ev_keyswitch(ev, P, D, d_gk, count, s));
+    EV_HIP(ev_galois_finish(ev->h, ev->d, d_c, T, P, count, s));
+    return MI355NTT_OK;
 }
 
 }  // extern "C"

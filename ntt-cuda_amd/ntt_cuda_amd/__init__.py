@@ -93,6 +93,14 @@ _SIGNATURES = {
     "mi355ntt_bfv_multiply": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_uint, vp, vp]),
     "mi355ntt_bfv_relinearize": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_uint, vp, vp]),
     "mi355ntt_bfv_multiply_relin": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_uint, vp, vp]),
+    "mi355ntt_bfv_add_plain": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_uint, vp]),
+    "mi355ntt_bfv_sub_plain": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_uint, vp]),
+    "mi355ntt_bfv_plain_ntt": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint, vp]),
+    "mi355ntt_bfv_multiply_plain": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_uint, vp, vp]),
+    "mi355ntt_bfv_multiply_plain_ntt": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_uint, ctypes.c_int, vp, vp]),
+    "mi355ntt_bfv_galois_keygen": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint, vp, vp, vp]),
+    "mi355ntt_bfv_galois_keygen_rns": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(ctypes.c_uint), ctypes.c_uint, vp, vp, u64, vp]),
+    "mi355ntt_bfv_apply_galois": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_uint, ctypes.c_uint, vp, vp]),
     "mi355ntt_shard_range": (ctypes.c_int, [ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, u32p, u32p]),
     "mi355ntt_shards_create": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.c_uint, ctypes.c_uint]),
     "mi355ntt_shards_destroy": (ctypes.c_int, [vp]),

@@ -156,7 +156,9 @@ def aux_primes(n, r):
 
 class BFVEvaluator:
     """Homomorphic evaluation on the ciphertexts of a BFVContext (C ABI section "BFV evaluation"): add, sub, multiply (BEHZ tensor
-    product and t/Q rescale), relinearize and both fused.  Ciphertexts are [2][count][num_primes][n] as encrypt_batch writes them
+    product and t/Q rescale), relinearize and both fused; plaintext operands (add_plain, sub_plain, plain_ntt, multiply_plain,
+    multiply_plain_ntt) and Galois automorphisms (galois_keygen, galois_keygen_rns, apply_galois).  Plaintexts are [count][n] words
+    taken mod t; a galois key is [r][2][num_primes][n].  Ciphertexts are [2][count][num_primes][n] as encrypt_batch writes them
     (count = 1: [2][num_primes][n]); the product before relinearization is [3][count][num_primes][n]; the relinearization key is
     [r][2][num_primes][n], r = num_primes - 1.  Scratch is allocated per call from torch's caching allocator, on the launch stream,
     unless passed; a caller-owned scratch buffer must not be shared by calls that may run concurrently."""
@@ -266,4 +268,70 @@ class BFVEvaluator:
         R = self.num_primes
         args = (self._p(c, 2 * count * R), self._p(a, 2 * count * R), self._p(b, 2 * count * R), self._p(rlk, 2 * self.r * R), int(count))
         self._launch(lambda scr, s: _check(lib().mi355ntt_bfv_multiply_relin(self._h, *args, scr, s), "mi355ntt_bfv_multiply_relin"), count,
+                     scratch, stream)
+
+    def add_plain(self, c, a, m, count=1, stream=None):
+        """c = (c0 + E(m), c1), E(m) encryption's encoding of m"""
+        from . import lib, _check, _stream
+        w = 2 * count * self.num_primes
+        _check(lib().mi355ntt_bfv_add_plain(self._h, self._p(c, w), self._p(a, w), self._p(m, count), int(count), _stream(stream)),
+               "mi355ntt_bfv_add_plain")
+
+    def sub_plain(self, c, a, m, count=1, stream=None):
+        from . import lib, _check, _stream
+        w = 2 * count * self.num_primes
+        _check(lib().mi355ntt_bfv_sub_plain(self._h, self._p(c, w), self._p(a, w), self._p(m, count), int(count), _stream(stream)),
+               "mi355ntt_bfv_sub_plain")
+
+    def plain_ntt(self, mhat, m, count=1, stream=None):
+        """mhat [count][r][n]: the centred lift of m in the NTT domain over Q, the operand of multiply_plain_ntt"""
+        from . import lib, _check, _stream
+        _check(lib().mi355ntt_bfv_plain_ntt(self._h, self._p(mhat, count * self.r), self._p(m, count), int(count), _stream(stream)),
+               "mi355ntt_bfv_plain_ntt")
+
+    def multiply_plain(self, c, a, m, count=1, scratch=None, stream=None):
+        from . import lib, _check
+        w = 2 * count * self.num_primes
+        args = (self._p(c, w), self._p(a, w), self._p(m, count), int(count))
+        self._launch(lambda scr, s: _check(lib().mi355ntt_bfv_multiply_plain(self._h, *args, scr, s), "mi355ntt_bfv_multiply_plain"), count,
+                     scratch, stream)
+
+    def multiply_plain_ntt(self, c, a, mhat, count=1, shared=False, scratch=None, stream=None):
+        """shared=False: mhat [count][r][n], one plaintext per ciphertext; shared=True: mhat [r][n] for the whole batch"""
+        from . import lib, _check
+        w = 2 * count * self.num_primes
+        args = (self._p(c, w), self._p(a, w), self._p(mhat, (1 if shared else count) * self.r), int(count), 1 if shared else 0)
+        self._launch(lambda scr, s: _check(lib().mi355ntt_bfv_multiply_plain_ntt(self._h, *args, scr, s), "mi355ntt_bfv_multiply_plain_ntt"),
+                     count, scratch, stream)
+
+    def galois_keygen(self, gk, secret_key, g, a, e, stream=None):
+        """key for Galois element g from explicit samples (as relin_keygen)"""
+        from . import lib, _check, _stream
+        R, r = self.num_primes, self.r
+        _check(lib().mi355ntt_bfv_galois_keygen(self._h, self._p(gk, 2 * r * R), self._p(secret_key, R), int(g), self._p(a, r * R),
+                                                self._p(e, r * R), _stream(stream)), "mi355ntt_bfv_galois_keygen")
+
+    def galois_random_bytes(self, num_g=1):
+        return int(num_g) * self.r * self.bfv.keygen_random_bytes
+
+    def galois_keygen_rns(self, gk, secret_key, gs, rnd, temp, nonce, stream=None):
+        """the complete key generation for the elements gs, gk [len(gs)][r][2][num_primes][n]; `nonce` has no default: a fresh one per
+        call"""
+        import ctypes
+        from . import lib, _check, _byte_ptr, _stream
+        R, r = self.num_primes, self.r
+        gs = [int(g) for g in gs]
+        assert rnd.numel() >= self.galois_random_bytes(len(gs))
+        arr = (ctypes.c_uint * max(1, len(gs)))(*gs)
+        _check(lib().mi355ntt_bfv_galois_keygen_rns(self._h, self._p(gk, len(gs) * 2 * r * R), self._p(secret_key, R), arr, len(gs),
+                                                    _byte_ptr(rnd), self._p(temp, R), int(nonce), _stream(stream)),
+               "mi355ntt_bfv_galois_keygen_rns")
+
+    def apply_galois(self, c, a, gk, g, count=1, scratch=None, stream=None):
+        """c = tau_g(a) key-switched back to s with g's key gk"""
+        from . import lib, _check
+        R = self.num_primes
+        w = 2 * count * R
+        args = (self._p(c, w), self._p(a, w), self._p(gk, 2 * self.r * R), int(g), int(count))
+        self._launch(lambda scr, s: _check(lib().mi355ntt_bfv_apply_galois(self._h, *args, scr, s), "mi355ntt_bfv_apply_galois"), count,
                      scratch, stream)
