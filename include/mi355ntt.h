@@ -501,6 +501,45 @@ int mi355ntt_bfv_galois_keygen_rns(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_
 int mi355ntt_bfv_apply_galois(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_gk,
                               unsigned g, unsigned count, void* d_scratch, mi355ntt_stream stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Hoisted Galois automorphisms ("Hoisted Galois automorphisms and their weighted sum"): many automorphisms of ONE
+ * ciphertext batch.  The digit split of c1 and its r^2 forward transforms do not depend on g, and tau_g commutes with the transform as
+ * a permutation of NTT slots, so G elements cost r^2 + 2 r G transforms per ciphertext instead of G (r^2 + 2 r), and their (weighted)
+ * sum r^2 + r forward and 2 r inverse transforms whatever G is.  gs is a HOST array of num_g >= 1 Galois elements (odd,
+ * 1 <= g < 2n, not necessarily distinct); d_gk is [num_g][r][2][num_primes][n] as mi355ntt_bfv_galois_keygen_rns writes it for the
+ * same gs.  With D_i = [c1]_{q_i} the RNS digits of the INPUT's c1 (canonical, lifted to every q_j by plain reduction),
+ *     H_g(a) = ( tau_g(c0) + sum_i tau_g(D_i) gk_g[i][0] ,  sum_i tau_g(D_i) gk_g[i][1] )      mod (x^n + 1, q_j), exactly.
+ * H_g(a) is NOT word for word mi355ntt_bfv_apply_galois(a, g): that call splits tau_g(c1) into canonical digits, this one permutes
+ * the digits of c1, so where tau_g negates a coefficient digit i contributes -x instead of q_i - x.  Both are valid decompositions
+ * (|tau_g(D_i)| < q_i, sum_i tau_g(D_i) g_i = tau_g(c1) mod Q), both decrypt to tau_g(m), and apply_galois' noise bound
+ * |v'| <= |v| + 1 + r n max(q_i) B_e holds for H_g unchanged.  For g = 1 nothing is negated and the two agree.
+ *   - Outputs are canonical on the Q slots; the special slot of every output is left untouched.
+ *   - Every g is checked before anything is launched: a bad one, num_g = 0, a null pointer (d_weights excepted) or a count outside
+ *     1 .. 65535 gives MI355NTT_EINVAL with no memory touched.
+ *   - Launches go on the caller's stream only; gs is read during the call (not afterwards) and travels as kernel arguments, so the
+ *     calls can be captured into a graph.
+ *   - Scratch is mi355ntt_bfv_eval_scratch_bytes(ev, count), unchanged.  galois_sum uses r^2 + 3 r polynomials per ciphertext.
+ *     apply_galois_hoisted keeps the r^2 digits and works through gs in groups of mi355ntt_bfv_hoist_group(ev) elements, as many as
+ *     the rest of the buffer holds 2 r products for: min(8, floor((max(8 r + 4, r^2 + 2 r) + 3 num_primes - r^2) / (2 r))), a function
+ *     of r only (r = 1: 8, 2: 6, 3: 5, 4: 4, 5 and 6: 3, 7 .. 15: 2).
+ * Noise: each H_g as apply_galois; galois_sum without weights |v'| <= G (|v| + 1 + r n max(q_i) B_e) + (G - 1); with weights
+ * |v'| <= G ((n t / 2)(|v| + 1 + r n max(q_i) B_e) + n (t - 1) / 2) + (G - 1).
+ * ---------------------------------------------------------------------------------------------- */
+/* elements per group of mi355ntt_bfv_apply_galois_hoisted (0 for a null evaluator) */
+unsigned mi355ntt_bfv_hoist_group(const mi355ntt_bfv_eval* ev);
+/* d_c_out [num_g][2][count][num_primes][n]: ciphertext batch k = H_{gs[k]}(d_a).  d_c_out must not overlap d_a (the input's c0 is
+ * read again for every group). */
+int mi355ntt_bfv_apply_galois_hoisted(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c_out, const mi355ntt_u64* d_a,
+                                      const mi355ntt_u64* d_gk, const unsigned* gs, unsigned num_g, unsigned count, void* d_scratch,
+                                      mi355ntt_stream stream);
+/* d_c [2][count][num_primes][n] = sum_k w~_k H_{gs[k]}(d_a); d_c may alias d_a.  d_weights is [num_g][r][n], what
+ * mi355ntt_bfv_plain_ntt writes for num_g plaintexts (centred lift, NTT domain), shared by all count ciphertexts; a null d_weights
+ * means every w~_k = 1.  The sum over k is taken in the NTT domain: r^2 + r forward and 2 r inverse transforms per ciphertext for
+ * any num_g.  Decrypts to sum_k m_k * tau_{gs[k]}(m) mod (x^n + 1, t) (without weights: sum_k tau_{gs[k]}(m)). */
+int mi355ntt_bfv_galois_sum(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_gk,
+                            const unsigned* gs, unsigned num_g, const mi355ntt_u64* d_weights, unsigned count, void* d_scratch,
+                            mi355ntt_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,8 @@ constexpr unsigned kEvalMaxQ = 15;                 // r = |Q| <= 15: B_sk = r + 
 constexpr unsigned kEvalMaxBsk = kEvalMaxQ + 1;
 constexpr unsigned kEvalBlock = 256;               // threads per block of every evaluator kernel
 constexpr unsigned kEvalMaxCount = 65535;          // ciphertexts per call: the kernels put the ciphertext index in gridDim.z
+constexpr unsigned kHoistMaxGroup = 8;             // elements per inner-product launch of apply_galois_hoisted (r = 1 reaches it)
+constexpr unsigned kHoistSumChunk = 16;            // elements per inner-product launch of galois_sum
 
 // One modulus of the evaluator's element-wise arithmetic.  Every product is exact for q < 2^62, whatever the modulus (the
 // Barrett-inexact ones of a literal BFV object included): x mod q for any 64-bit x by m64, 128-bit sums folded by 2^64 mod q.
@@ -85,5 +87,23 @@ hipError_t ev_galois_digits(const EvConsts& h, const EvConsts* d, u64* D, u64* T
 hipError_t ev_galois_finish(const EvConsts& h, const EvConsts* d, u64* out, const u64* T, const u64* P, unsigned count, hipStream_t s);
 // galois key i: slot 0 (holding NTT(e_i)) <- -(a_i s + NTT(e_i)) + [j == i] tau_g(s), slot 1 = a_i untouched; gk [r][2][R][n]
 hipError_t ev_galois_key(const EvConsts& h, const EvConsts* d, u64* gk, const u64* s_hat, unsigned g, hipStream_t s);
+
+// ---- launchers (kernels_bfv_hoist.hip): hoisted Galois automorphisms.  Dhat [count][r][r][n] is ev_galois_digits' D with ginv = 1
+// after the forward transform; the elements travel as kernel arguments (no device copy: the calls can be captured into a graph).
+struct HoistElems {
+    unsigned g[kHoistMaxGroup], ginv[kHoistMaxGroup];
+};
+struct HoistSumElems {
+    unsigned g[kHoistSumChunk];
+};
+// P [elems][2][count][r][n]: P[e][h][z][j][k] = sum_i Dhat[z][i][j][k'] gk[e][i][h][j][k], k' the NTT-slot permutation of el.g[e]
+hipError_t ev_hoist_dot(const EvConsts& h, const EvConsts* d, u64* P, const u64* D, const u64* gk, const HoistElems& el, unsigned elems,
+                        unsigned count, hipStream_t s);
+// P [2][count][r][n] = (first ? 0 : P) + sum_e w[e][j] (that inner product + [h == 0] That[z][j][k']); w [elems][r][n] or nullptr (all 1)
+hipError_t ev_hoist_sum(const EvConsts& h, const EvConsts* d, u64* P, const u64* D, const u64* T, const u64* gk, const u64* w,
+                        const HoistSumElems& el, unsigned elems, bool first, unsigned count, hipStream_t s);
+// out [elems][2][count][R][n]: c0 = tau_g(a's c0) + P0 (gathered from a with el.ginv[e]), c1 = P1; P after the inverse transform
+hipError_t ev_hoist_finish(const EvConsts& h, const EvConsts* d, u64* out, const u64* a, const u64* P, const HoistElems& el,
+                           unsigned elems, unsigned count, hipStream_t s);
 
 }  // namespace mi355ntt

@@ -1,7 +1,7 @@
 // bfv_eval_host.cpp -- the BFV evaluator (C ABI section "BFV evaluation" of include/mi355ntt.h): auxiliary prime search, BEHZ
 // constants, relinearization and Galois key generation and the drivers.  Transforms run through the evaluator's two exact contexts
-// (one over Q, one over B_sk); the element-wise RNS steps through kernels_bfv_eval.hip and kernels_bfv_galois.hip.  DESIGN.md, "BFV evaluation", states the algorithm
-// and the bounds the constants below rely on.
+// (one over Q, one over B_sk); the element-wise RNS steps through kernels_bfv_eval.hip, kernels_bfv_galois.hip and
+// kernels_bfv_hoist.hip.  DESIGN.md, "BFV evaluation", states the algorithm and the bounds the constants below rely on.
 #include "../../include/mi355ntt.h"
 
 #include <hip/hip_runtime.h>
@@ -264,6 +264,29 @@ unsigned ev_galois_inverse(unsigned g, unsigned n)
 
 // Scratch polynomials per ciphertext: apply_galois r^2 + 3 r (digits, products, the staged tau_g(c0)), multiply_plain 3 r (the dense
 // copies and the lifted plaintext).  Both fit in mi355ntt_bfv_eval_scratch_bytes's max(8 r + 4, r^2 + 2 r) + 3 (r + 1).
+
+// Hoisted automorphisms.  Scratch polynomials per ciphertext of mi355ntt_bfv_eval_scratch_bytes, and the number of elements whose
+// 2 r products fit next to the r^2 digits: a function of r only (r = 1: 8, 2: 6, 3: 5, 4: 4, 5 and 6: 3, 7 .. 15: 2), never below 1
+// since r^2 + 2 r <= relin_polys(r).
+size_t scratch_polys(unsigned r)
+{
+    const size_t m = mult_polys(r), rl = relin_polys(r);
+    return (m > rl ? m : rl) + 3 * ((size_t)r + 1);
+}
+unsigned hoist_group(unsigned r)
+{
+    const size_t g = (scratch_polys(r) - (size_t)r * r) / (2 * (size_t)r);
+    return g < kHoistMaxGroup ? (unsigned)g : kHoistMaxGroup;
+}
+
+// the checks both hoisted calls make before they touch memory: every element odd and below 2n, 1 <= count <= kEvalMaxCount
+int ev_hoist_args_ok(const mi355ntt_bfv_eval* ev, const unsigned* gs, unsigned num_g, unsigned count)
+{
+    if (num_g == 0 || count == 0 || count > kEvalMaxCount) return MI355NTT_EINVAL;
+    for (unsigned k = 0; k < num_g; k++)
+        if (!ev_galois_ok(ev, gs[k])) return MI355NTT_EINVAL;
+    return MI355NTT_OK;
+}
 
 // The keystream key of Galois keys: neither keygen_rns's (32 x 0x01) nor relinearization's (32 x 0x02), for the reason kRelinKey gives.
 const unsigned char kGaloisKey[32] = {3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3};
@@ -591,6 +614,65 @@ int mi355ntt_bfv_apply_galois(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, co
     EV_HIP(ev_galois_digits(ev->h, ev->d, D, T, d_a, ev_galois_inverse(g, n), count, s));
     EV_RC(ev_keyswitch(ev, P, D, d_gk, count, s));
     EV_HIP(ev_galois_finish(ev->h, ev->d, d_c, T, P, count, s));
+    return MI355NTT_OK;
+}
+
+unsigned mi355ntt_bfv_hoist_group(const mi355ntt_bfv_eval* ev) { return ev ? hoist_group(ev->r) : 0; }
+
+int mi355ntt_bfv_apply_galois_hoisted(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c_out, const mi355ntt_u64* d_a, const mi355ntt_u64* d_gk,
+                                      const unsigned* gs, unsigned num_g, unsigned count, void* d_scratch, mi355ntt_stream stream)
+{
+    if (!ev || !d_c_out || !d_a || !d_gk || !gs || !d_scratch) return MI355NTT_EINVAL;
+    EV_RC(ev_hoist_args_ok(ev, gs, num_g, count));
+    DeviceScope scope(ev->device);
+    EV_HIP(scope.err);
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned r = ev->r, n = ev->n, group = hoist_group(r);
+    const size_t R = ev->R;
+    u64* D = static_cast<u64*>(d_scratch);                       // [count][r][r][n]
+    u64* P = D + (size_t)count * r * r * n;                      // [group][2][count][r][n]
+    // the digits of c1 itself (g = 1); the staged copy of c0 that comes with them lands in P's space and is not used
+    EV_HIP(ev_galois_digits(ev->h, ev->d, D, P, d_a, 1, count, s));
+    EV_RC(mi355ntt_forward_batch(ev->ctx_q, D, count * r * r, r, s));
+    for (unsigned k0 = 0; k0 < num_g; k0 += group) {
+        const unsigned elems = num_g - k0 < group ? num_g - k0 : group;
+        HoistElems el = {};
+        for (unsigned e = 0; e < elems; e++) {
+            el.g[e] = gs[k0 + e];
+            el.ginv[e] = ev_galois_inverse(gs[k0 + e], n);
+        }
+        EV_HIP(ev_hoist_dot(ev->h, ev->d, P, D, d_gk + (size_t)k0 * r * 2 * R * n, el, elems, count, s));
+        EV_RC(mi355ntt_inverse_batch(ev->ctx_q, P, elems * 2 * count * r, r, s));
+        EV_HIP(ev_hoist_finish(ev->h, ev->d, d_c_out + (size_t)k0 * 2 * count * R * n, d_a, P, el, elems, count, s));
+    }
+    return MI355NTT_OK;
+}
+
+int mi355ntt_bfv_galois_sum(const mi355ntt_bfv_eval* ev, mi355ntt_u64* d_c, const mi355ntt_u64* d_a, const mi355ntt_u64* d_gk,
+                            const unsigned* gs, unsigned num_g, const mi355ntt_u64* d_weights, unsigned count, void* d_scratch,
+                            mi355ntt_stream stream)
+{
+    if (!ev || !d_c || !d_a || !d_gk || !gs || !d_scratch) return MI355NTT_EINVAL;
+    EV_RC(ev_hoist_args_ok(ev, gs, num_g, count));
+    DeviceScope scope(ev->device);
+    EV_HIP(scope.err);
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned r = ev->r, n = ev->n;
+    const size_t R = ev->R;
+    u64* D = static_cast<u64*>(d_scratch);                       // [count][r][r][n]
+    u64* T = D + (size_t)count * r * r * n;                      // [count][r][n]: c0, transformed with the digits in one batch
+    u64* P = T + (size_t)count * r * n;                          // [2][count][r][n]
+    EV_HIP(ev_galois_digits(ev->h, ev->d, D, T, d_a, 1, count, s));
+    EV_RC(mi355ntt_forward_batch(ev->ctx_q, D, count * r * (r + 1), r, s));
+    for (unsigned k0 = 0; k0 < num_g; k0 += kHoistSumChunk) {
+        const unsigned elems = num_g - k0 < kHoistSumChunk ? num_g - k0 : kHoistSumChunk;
+        HoistSumElems el = {};
+        for (unsigned e = 0; e < elems; e++) el.g[e] = gs[k0 + e];
+        EV_HIP(ev_hoist_sum(ev->h, ev->d, P, D, T, d_gk + (size_t)k0 * r * 2 * R * n, d_weights ? d_weights + (size_t)k0 * r * n : nullptr,
+                            el, elems, k0 == 0, count, s));
+    }
+    EV_RC(mi355ntt_inverse_batch(ev->ctx_q, P, 2 * count * r, r, s));
+    EV_HIP(ev_plain_copy(ev->h, ev->d, d_c, P, count, false, s));
     return MI355NTT_OK;
 }
 

@@ -101,6 +101,9 @@ _SIGNATURES = {
     "mi355ntt_bfv_galois_keygen": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint, vp, vp, vp]),
     "mi355ntt_bfv_galois_keygen_rns": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(ctypes.c_uint), ctypes.c_uint, vp, vp, u64, vp]),
     "mi355ntt_bfv_apply_galois": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_uint, ctypes.c_uint, vp, vp]),
+    "mi355ntt_bfv_hoist_group": (ctypes.c_uint, [vp]),
+    "mi355ntt_bfv_apply_galois_hoisted": (ctypes.c_int, [vp, vp, vp, vp, ctypes.POINTER(ctypes.c_uint), ctypes.c_uint, ctypes.c_uint, vp, vp]),
+    "mi355ntt_bfv_galois_sum": (ctypes.c_int, [vp, vp, vp, vp, ctypes.POINTER(ctypes.c_uint), ctypes.c_uint, vp, ctypes.c_uint, vp, vp]),
     "mi355ntt_shard_range": (ctypes.c_int, [ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, u32p, u32p]),
     "mi355ntt_shards_create": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.c_uint, ctypes.c_uint]),
     "mi355ntt_shards_destroy": (ctypes.c_int, [vp]),

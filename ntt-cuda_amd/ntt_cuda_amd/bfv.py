@@ -157,7 +157,8 @@ def aux_primes(n, r):
 class BFVEvaluator:
     """Homomorphic evaluation on the ciphertexts of a BFVContext (C ABI section "BFV evaluation"): add, sub, multiply (BEHZ tensor
     product and t/Q rescale), relinearize and both fused; plaintext operands (add_plain, sub_plain, plain_ntt, multiply_plain,
-    multiply_plain_ntt) and Galois automorphisms (galois_keygen, galois_keygen_rns, apply_galois).  Plaintexts are [count][n] words
+    multiply_plain_ntt) and Galois automorphisms (galois_keygen, galois_keygen_rns, apply_galois; many elements of one ciphertext
+    batch at once: apply_galois_hoisted, galois_sum).  Plaintexts are [count][n] words
     taken mod t; a galois key is [r][2][num_primes][n].  Ciphertexts are [2][count][num_primes][n] as encrypt_batch writes them
     (count = 1: [2][num_primes][n]); the product before relinearization is [3][count][num_primes][n]; the relinearization key is
     [r][2][num_primes][n], r = num_primes - 1.  Scratch is allocated per call from torch's caching allocator, on the launch stream,
@@ -334,4 +335,37 @@ class BFVEvaluator:
         w = 2 * count * R
         args = (self._p(c, w), self._p(a, w), self._p(gk, 2 * self.r * R), int(g), int(count))
         self._launch(lambda scr, s: _check(lib().mi355ntt_bfv_apply_galois(self._h, *args, scr, s), "mi355ntt_bfv_apply_galois"), count,
+                     scratch, stream)
+
+    @property
+    def hoist_group(self):
+        """elements per scratch group of apply_galois_hoisted (a function of r only)"""
+        from . import lib
+        return int(lib().mi355ntt_bfv_hoist_group(self._h))
+
+    def apply_galois_hoisted(self, c_out, a, gk, gs, count=1, scratch=None, stream=None):
+        """c_out [len(gs)][2][count][num_primes][n]: batch k = H_{gs[k]}(a), the automorphism with the digits of a's c1 split and
+        transformed once for all elements; gk [len(gs)][r][2][num_primes][n] as galois_keygen_rns writes it for gs.  c_out must not
+        overlap a.  Not word for word apply_galois (another valid digit decomposition); decrypts to the same plaintext."""
+        import ctypes
+        from . import lib, _check
+        R = self.num_primes
+        gs = [int(g) for g in gs]
+        arr = (ctypes.c_uint * max(1, len(gs)))(*gs)
+        args = (self._p(c_out, len(gs) * 2 * count * R), self._p(a, 2 * count * R), self._p(gk, len(gs) * 2 * self.r * R), arr, len(gs),
+                int(count))
+        self._launch(lambda scr, s: _check(lib().mi355ntt_bfv_apply_galois_hoisted(self._h, *args, scr, s),
+                                           "mi355ntt_bfv_apply_galois_hoisted"), count, scratch, stream)
+
+    def galois_sum(self, c, a, gk, gs, count=1, weights=None, scratch=None, stream=None):
+        """c = sum_k w_k H_{gs[k]}(a), summed in the NTT domain; weights [len(gs)][r][n] from plain_ntt(count=len(gs)), shared by the
+        batch, or None for every w_k = 1.  c may alias a."""
+        import ctypes
+        from . import lib, _check, vp
+        R = self.num_primes
+        gs = [int(g) for g in gs]
+        arr = (ctypes.c_uint * max(1, len(gs)))(*gs)
+        w = vp(0) if weights is None else self._p(weights, len(gs) * self.r)
+        args = (self._p(c, 2 * count * R), self._p(a, 2 * count * R), self._p(gk, len(gs) * 2 * self.r * R), arr, len(gs), w, int(count))
+        self._launch(lambda scr, s: _check(lib().mi355ntt_bfv_galois_sum(self._h, *args, scr, s), "mi355ntt_bfv_galois_sum"), count,
                      scratch, stream)
