@@ -171,7 +171,7 @@ class EvalModel:
         return out
 
     def relinearize(self, c3, rlk):
-        c3 = np.asarray(c3, dtype=np.uint64)
+        c3 = self.canon(c3)                                  # a word equal to q_i is the digit 0 in EVERY slot j, not only j = i
         rlk = np.asarray(rlk, dtype=np.uint64)
         out = self._out(2)
         for j, (qj, wj) in enumerate(zip(self.qs, self.psis)):
