@@ -5,48 +5,11 @@
 // their per-coefficient residue vectors live in registers.
 #include <utility>
 
-#include "bfv_eval.hpp"
-#include "modarith.cuh"
+#include "bfv_eval_arith.cuh"
 
 namespace mi355ntt {
 
 namespace {
-
-// x mod q for any 64-bit x: the estimate floor(x m64 / 2^64) is the quotient or up to two less (kernels_bfv.hip, reduce64)
-__device__ __forceinline__ u64 red64(u64 x, const EvPrime& p)
-{
-    u64 r = x - mul_hi(x, p.m64) * p.q;
-    r = r >= p.q ? r - p.q : r;
-    return r >= p.q ? r - p.q : r;
-}
-
-// 128-bit accumulator.  Every sum here has at most r + 2 <= 17 terms, each a product of two words below 2^61: < 2^127.
-struct Acc {
-    u64 lo = 0, hi = 0;
-    __device__ __forceinline__ void mac(u64 a, u64 b)
-    {
-        u64 l, h;
-        mul_wide(a, b, l, h);
-        lo += l;
-        hi += h + (lo < l);
-    }
-    __device__ __forceinline__ void add(u64 a)
-    {
-        lo += a;
-        hi += (lo < a);
-    }
-};
-
-// {hi, lo} mod q: hi 2^64 by the Shoup product with 2^64 mod q (any 64-bit hi, result below 2q), lo by red64; sum below 3q < 2^64
-__device__ __forceinline__ u64 red128(const Acc& a, const EvPrime& p)
-{
-    u64 s = shoup_mul_lazy(a.hi, p.r64, p.r64p, p.q) + red64(a.lo, p);
-    s = s >= p.q ? s - p.q : s;
-    return s >= p.q ? s - p.q : s;
-}
-
-// x w mod q for a constant w < q with Shoup companion wp; any 64-bit x
-__device__ __forceinline__ u64 mulc(u64 x, u64 w, u64 wp, u64 q) { return csub(shoup_mul_lazy(x, w, wp, q), q); }
 
 // ---- Q -> B_sk with m~ = 2^32 (BEHZ Algorithms 2 + 3).  tmp_i = [x_i m~ (Q/q_i)^-1]_{q_i}; sum_i tmp_i (Q/q_i) = [m~ x]_Q + alpha Q,
 // 0 <= alpha < r.  r_m = -(that) Q^-1 mod m~, centred, makes the sum plus r_m Q divisible by m~; the quotient is x or x - Q (|.| < Q),
@@ -97,7 +60,7 @@ k_tensor(const EvConsts* __restrict__ c, u64* __restrict__ xq, u64* __restrict__
     const bool inq = p < r;
     const unsigned np = inq ? r : r + 1, slot = inq ? p : p - r;
     const EvPrime pr = inq ? c->q[slot] : c->b[slot];
-    u64* base = (inq ? xq : xb) + ((size_t)z * np + slot) * n + k;
+    u64* base = (inq ? xq : xb) + dense_word(0, z, slot, k, count, np, n);
     const size_t cs = (size_t)count * np * n;
     const u64 a0 = base[0], a1 = base[cs], b0 = base[2 * cs], b1 = base[3 * cs];
     Acc d0, d1, d2;
@@ -167,7 +130,7 @@ k_digits(const EvConsts* __restrict__ c, u64* __restrict__ D, const u64* __restr
     const u64 qi = c->q[i].q;
     u64 x = c3[((size_t)2 * count + z) * (r + 1) * n + (size_t)i * n + k];
     x = x >= qi ? x - qi : x;
-    u64* d = D + ((size_t)z * r + i) * r * n + k;
+    u64* d = D + ((size_t)z * r + i) * r * n + k;              // (k_galois_digits has this loop too: see bfv_eval_arith.cuh)
     for (unsigned j = 0; j < r; j++) d[(size_t)j * n] = j == i ? x : red64(x, c->q[j]);
 }
 
@@ -214,7 +177,7 @@ k_relin_key(const EvConsts* __restrict__ c, u64* __restrict__ rlk, const u64* __
     const EvPrime p = c->q[j];
     u64* k0 = rlk + ((size_t)i * 2 * R + j) * n + k;
     const u64 a = k0[R * n], s = s_hat[(size_t)j * n + k];
-    Acc acc;
+    Acc acc;                                            // (mac_red, written out: through it this kernel's instructions reorder)
     acc.mac(a, s);
     acc.add(k0[0]);
     u64 v = red128(acc, p);

@@ -2,32 +2,11 @@
 // DESIGN.md "Plaintext operands and Galois automorphisms").  The transforms, the fused products and the key-switch inner product are
 // the contexts' calls and kernels_bfv_eval.hip's k_relin_dot; these kernels do the plaintext encoding and lift, the canonical copies
 // around the fused products, the coefficient automorphism fused into the digit split, and the galois key's NTT-slot permutation.
-#include "bfv_eval.hpp"
-#include "modarith.cuh"
+#include "bfv_eval_arith.cuh"
 
 namespace mi355ntt {
 
 namespace {
-
-// x mod q for any 64-bit x (kernels_bfv_eval.hip, red64)
-__device__ __forceinline__ u64 g_red64(u64 x, const EvPrime& p)
-{
-    u64 r = x - mul_hi(x, p.m64) * p.q;
-    r = r >= p.q ? r - p.q : r;
-    return r >= p.q ? r - p.q : r;
-}
-
-// {hi, lo} of a b + c mod q (kernels_bfv_eval.hip, Acc + red128); a, b < 2^62, c < 2^64
-__device__ __forceinline__ u64 g_mac_red(u64 a, u64 b, u64 c, const EvPrime& p)
-{
-    u64 lo, hi;
-    mul_wide(a, b, lo, hi);
-    lo += c;
-    hi += (lo < c);
-    u64 s = shoup_mul_lazy(hi, p.r64, p.r64p, p.q) + g_red64(lo, p);
-    s = s >= p.q ? s - p.q : s;
-    return s >= p.q ? s - p.q : s;
-}
 
 // ---- c0 +/- E(m), c1 copied, every output canonical.  E(m) is encryption's encoding (k_encrypt_tail, the reference's weird_m_stuff):
 // m floor(q_j / t) + fix with fix = floor((m + (t + 1) / 2) / t), m taken mod t (a mask: t is a power of two).
@@ -58,7 +37,7 @@ k_plain_lift(const EvConsts* __restrict__ c, u64* __restrict__ mhat, const u64* 
     const unsigned k = blockIdx.x * kEvalBlock + threadIdx.x;
     const u64 q = c->q[j].q, t = c->t;
     const u64 mi = m[(size_t)z * n + k] & (t - 1);
-    mhat[((size_t)z * r + j) * n + k] = mi >= (t >> 1) && mi ? q - (t - mi) : mi;
+    mhat[poly_word(z, j, k, r, n)] = mi >= (t >> 1) && mi ? q - (t - mi) : mi;
 }
 
 // ---- canonical copy between the R-strided ciphertext layout [2][count][R][n] and the dense [2][count][r][n]: to_dense reads the
@@ -98,6 +77,7 @@ k_galois_digits(const EvConsts* __restrict__ c, u64* __restrict__ D, u64* __rest
     const bool c1 = p < r;
     const unsigned i = c1 ? p : p - r;
     const unsigned k = (blockIdx.x / 8) * kEvalBlock + threadIdx.x;
+    // (k_hoist_finish has this gather too, both written out: see bfv_eval_arith.cuh)
     const unsigned src = (ginv * k) & (2 * n - 1);              // ginv k mod 2n: 2n divides 2^32, the wrap is harmless
     const u64 qi = c->q[i].q;
     u64 x = a[(((size_t)(c1 ? count : 0) + z) * (r + 1) + i) * n + (src & (n - 1))];
@@ -107,8 +87,8 @@ k_galois_digits(const EvConsts* __restrict__ c, u64* __restrict__ D, u64* __rest
         T[((size_t)z * r + i) * n + k] = x;
         return;
     }
-    u64* d = D + ((size_t)z * r + i) * r * n + k;
-    for (unsigned j = 0; j < r; j++) d[(size_t)j * n] = j == i ? x : g_red64(x, c->q[j]);
+    u64* d = D + ((size_t)z * r + i) * r * n + k;              // (k_digits' loop, written out: see bfv_eval_arith.cuh)
+    for (unsigned j = 0; j < r; j++) d[(size_t)j * n] = j == i ? x : red64(x, c->q[j]);
 }
 
 // ---- key-switch result: out c0 = T + P0 (T: the staged tau_g(c0)), c1 = P1; P [2][count][r][n].  grid (n / kEvalBlock, 2 r, count)
@@ -124,9 +104,8 @@ k_galois_finish(const EvConsts* __restrict__ c, u64* __restrict__ out, const u64
     out[(((size_t)h * count + z) * (r + 1) + j) * n + k] = x;
 }
 
-// ---- galois key i, prime j: -(a s + e) + [i == j] tau_g(s) in the NTT domain; gk [r][2][R][n], slot 0 holding NTT(e_i).  Slot k of
-// the bit-reversed forward output holds s(psi^(2 brev(k) + 1)), so tau_g(s)'s slot k is s's slot k' with
-// 2 brev(k') + 1 = g (2 brev(k) + 1) mod 2n: a permutation, no transform.  grid (n / kEvalBlock, r (j), r (i))
+// ---- galois key i, prime j: -(a s + e) + [i == j] tau_g(s) in the NTT domain; gk [r][2][R][n], slot 0 holding NTT(e_i).  tau_g(s) is
+// a permutation of s_hat's slots (galois_slot), no transform.  grid (n / kEvalBlock, r (j), r (i))
 __global__ void __launch_bounds__(kEvalBlock)
 k_galois_key(const EvConsts* __restrict__ c, u64* __restrict__ gk, const u64* __restrict__ s_hat, unsigned g, unsigned lg, unsigned n)
 {
@@ -136,13 +115,9 @@ k_galois_key(const EvConsts* __restrict__ c, u64* __restrict__ gk, const u64* __
     const EvPrime p = c->q[j];
     u64* k0 = gk + ((size_t)i * 2 * R + j) * n + k;
     const u64 a = k0[R * n], s = s_hat[(size_t)j * n + k];
-    u64 v = g_mac_red(a, s, k0[0], p);
+    u64 v = mac_red(a, s, k0[0], p);                    // (-(a s + e) as k_relin_key has it, written out: see bfv_eval_arith.cuh)
     v = v ? p.q - v : 0;
-    if (i == j) {
-        const unsigned e = (g * (2 * (__brev(k) >> (32 - lg)) + 1)) & (2 * n - 1);
-        const unsigned kp = __brev((e - 1) >> 1) >> (32 - lg);
-        v = add_mod(v, s_hat[(size_t)j * n + kp], p.q);
-    }
+    if (i == j) v = add_mod(v, s_hat[(size_t)j * n + galois_slot(g, k, lg, n)], p.q);
     k0[0] = v;
 }
 
@@ -182,9 +157,7 @@ hipError_t ev_galois_finish(const EvConsts& h, const EvConsts* d, u64* out, cons
 
 hipError_t ev_galois_key(const EvConsts& h, const EvConsts* d, u64* gk, const u64* s_hat, unsigned g, hipStream_t s)
 {
-    unsigned lg = 0;
-    while ((1u << lg) < h.n) lg++;
-    k_galois_key<<<dim3(h.n / kEvalBlock, h.r, h.r), kEvalBlock, 0, s>>>(d, gk, s_hat, g, lg, h.n);
+    k_galois_key<<<dim3(h.n / kEvalBlock, h.r, h.r), kEvalBlock, 0, s>>>(d, gk, s_hat, g, log2_of(h.n), h.n);
     return hipGetLastError();
 }
 

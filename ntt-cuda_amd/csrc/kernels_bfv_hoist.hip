@@ -3,8 +3,7 @@
 // Q context's transforms); an automorphism then is a permutation of NTT slots, so every Galois element costs one permuted inner
 // product with its key, not r^2 more transforms.  These kernels are that inner product -- one ciphertext batch per element
 // (k_hoist_dot), or the (weighted) sum over the elements taken in the NTT domain (k_hoist_sum) -- and the hoisted form's finish.
-#include "bfv_eval.hpp"
-#include "modarith.cuh"
+#include "bfv_eval_arith.cuh"
 
 namespace mi355ntt {
 
@@ -14,70 +13,18 @@ namespace {
 // the ciphertext chunk is the fastest grid dimension, so the blocks that share a key tile are dispatched back to back.
 constexpr unsigned kHoistCts = 2;
 
-// x mod q for any 64-bit x (kernels_bfv_eval.hip, red64)
-__device__ __forceinline__ u64 h_red64(u64 x, const EvPrime& p)
-{
-    u64 r = x - mul_hi(x, p.m64) * p.q;
-    r = r >= p.q ? r - p.q : r;
-    return r >= p.q ? r - p.q : r;
-}
-
-// 128-bit accumulator (kernels_bfv_eval.hip, Acc): at most r + 2 <= 17 terms, each a product of two words below 2^61
-struct HAcc {
-    u64 lo = 0, hi = 0;
-    __device__ __forceinline__ void mac(u64 a, u64 b)
-    {
-        u64 l, h;
-        mul_wide(a, b, l, h);
-        lo += l;
-        hi += h + (lo < l);
-    }
-    __device__ __forceinline__ void add(u64 a)
-    {
-        lo += a;
-        hi += (lo < a);
-    }
-};
-
-__device__ __forceinline__ u64 h_red128(const HAcc& a, const EvPrime& p)
-{
-    u64 s = shoup_mul_lazy(a.hi, p.r64, p.r64p, p.q) + h_red64(a.lo, p);
-    s = s >= p.q ? s - p.q : s;
-    return s >= p.q ? s - p.q : s;
-}
-
-// a b + c mod q (kernels_bfv_galois.hip, g_mac_red); a, b < 2^62, c < 2^64
-__device__ __forceinline__ u64 h_mac_red(u64 a, u64 b, u64 c, const EvPrime& p)
-{
-    HAcc s;
-    s.mac(a, b);
-    s.add(c);
-    return h_red128(s, p);
-}
-
-// Slot k of the bit-reversed forward output holds x(psi^(2 brev(k) + 1)), so tau_g(x)'s slot k is x's slot k' with
-// 2 brev(k') + 1 = g (2 brev(k) + 1) mod 2n (k_galois_key).  The low bits of k are the high bits of brev(k), and
-// u -> g u + (g - 1) / 2 mod n keeps low bits among low bits: every aligned block of 2^b consecutive k maps onto one aligned block
-// of 2^b slots, permuted inside it.  A workgroup's 256 gathered words are the 2 KiB it would read without the permutation.
-__device__ __forceinline__ unsigned hoist_slot(unsigned g, unsigned k, unsigned lg, unsigned n)
-{
-    const unsigned e = (g * (2 * (__brev(k) >> (32 - lg)) + 1)) & (2 * n - 1);
-    return __brev((e - 1) >> 1) >> (32 - lg);
-}
-
 // a[zt][h] += sum_i Dhat[z0 + zt][i][j][kp] key[i][h][j][k] for zt < nz (block-uniform); Dhat [count][r][r][n], key [r][2][R][n]
-__device__ __forceinline__ void hoist_dot(HAcc (&a)[kHoistCts][2], const u64* __restrict__ D, const u64* __restrict__ key, unsigned r,
+__device__ __forceinline__ void hoist_dot(Acc (&a)[kHoistCts][2], const u64* __restrict__ D, const u64* __restrict__ key, unsigned r,
                                           unsigned j, unsigned k, unsigned kp, unsigned n, unsigned z0, unsigned nz)
 {
-    const size_t R = r + 1;
-    const u64* kq = key + (size_t)j * n + k;
-    const u64* dq = D + ((size_t)z0 * r * r + j) * n + kp;
+    const u64* kq = key + key_word(0, 0, j, k, r + 1, n);
+    const u64* dq = D + digit_word(z0, 0, j, kp, r, n);
     for (unsigned i = 0; i < r; i++) {
-        const u64 k0 = kq[(size_t)i * 2 * R * n], k1 = kq[((size_t)i * 2 + 1) * R * n];
+        const u64 k0 = kq[key_word(i, 0, 0, 0, r + 1, n)], k1 = kq[key_word(i, 1, 0, 0, r + 1, n)];
 #pragma unroll
         for (unsigned zt = 0; zt < kHoistCts; zt++) {
             if (zt < nz) {
-                const u64 d = dq[((size_t)zt * r + i) * r * n];
+                const u64 d = dq[digit_word(zt, i, 0, 0, r, n)];
                 a[zt][0].mac(d, k0);
                 a[zt][1].mac(d, k1);
             }
@@ -94,16 +41,16 @@ k_hoist_dot(const EvConsts* __restrict__ c, u64* __restrict__ P, const u64* __re
     const unsigned r = c->r, e = blockIdx.z / r, j = blockIdx.z % r;
     const unsigned z0 = blockIdx.x * kHoistCts, nz = min(kHoistCts, count - z0);
     const unsigned k = blockIdx.y * kEvalBlock + threadIdx.x;
-    const unsigned kp = hoist_slot(el.g[e], k, lg, n);
-    HAcc a[kHoistCts][2];
-    hoist_dot(a, D, gk + (size_t)e * r * 2 * (r + 1) * n, r, j, k, kp, n, z0, nz);
+    const unsigned kp = galois_slot(el.g[e], k, lg, n);
+    Acc a[kHoistCts][2];
+    hoist_dot(a, D, gk + key_word((size_t)e * r, 0, 0, 0, r + 1, n), r, j, k, kp, n, z0, nz);
     const EvPrime p = c->q[j];
 #pragma unroll
     for (unsigned zt = 0; zt < kHoistCts; zt++) {
         if (zt < nz) {
             u64* out = P + ((((size_t)e * 2) * count + z0 + zt) * r + j) * n + k;
-            out[0] = h_red128(a[zt][0], p);
-            out[(size_t)count * r * n] = h_red128(a[zt][1], p);
+            out[0] = red128(a[zt][0], p);
+            out[(size_t)count * r * n] = red128(a[zt][1], p);
         }
     }
 }
@@ -123,7 +70,7 @@ k_hoist_sum(const EvConsts* __restrict__ c, u64* __restrict__ P, const u64* __re
     const unsigned z0 = blockIdx.x * kHoistCts, nz = min(kHoistCts, count - z0);
     const unsigned k = blockIdx.y * kEvalBlock + threadIdx.x;
     const EvPrime p = c->q[j];
-    u64* out = P + ((size_t)z0 * r + j) * n + k;
+    u64* out = P + dense_word(0, z0, j, k, count, r, n);
     const size_t hs = (size_t)count * r * n, zs = (size_t)r * n;
     u64 s[kHoistCts][2];
 #pragma unroll
@@ -133,20 +80,20 @@ k_hoist_sum(const EvConsts* __restrict__ c, u64* __restrict__ P, const u64* __re
         s[zt][1] = load ? out[hs + zt * zs] : 0;
     }
     for (unsigned e = 0; e < elems; e++) {
-        const unsigned kp = hoist_slot(el.g[e], k, lg, n);
-        HAcc a[kHoistCts][2];
+        const unsigned kp = galois_slot(el.g[e], k, lg, n);
+        Acc a[kHoistCts][2];
 #pragma unroll
         for (unsigned zt = 0; zt < kHoistCts; zt++)
-            if (zt < nz) a[zt][0].add(T[((size_t)(z0 + zt) * r + j) * n + kp]);
-        hoist_dot(a, D, gk + (size_t)e * r * 2 * (r + 1) * n, r, j, k, kp, n, z0, nz);
-        const u64 we = w ? w[((size_t)e * r + j) * n + k] : 0;
+            if (zt < nz) a[zt][0].add(T[poly_word(z0 + zt, j, kp, r, n)]);
+        hoist_dot(a, D, gk + key_word((size_t)e * r, 0, 0, 0, r + 1, n), r, j, k, kp, n, z0, nz);
+        const u64 we = w ? w[poly_word(e, j, k, r, n)] : 0;
 #pragma unroll
         for (unsigned zt = 0; zt < kHoistCts; zt++) {
             if (zt < nz) {
 #pragma unroll
                 for (unsigned h = 0; h < 2; h++) {
-                    const u64 x = h_red128(a[zt][h], p);
-                    s[zt][h] = w ? h_mac_red(x, we, s[zt][h], p) : add_mod(s[zt][h], x, p.q);
+                    const u64 x = red128(a[zt][h], p);
+                    s[zt][h] = w ? mac_red(x, we, s[zt][h], p) : add_mod(s[zt][h], x, p.q);
                 }
             }
         }
@@ -173,20 +120,13 @@ k_hoist_finish(const EvConsts* __restrict__ c, u64* __restrict__ out, const u64*
     u64 x = P[(ehz * r + j) * n + k];
     if (h == 0) {
         const u64 q = c->q[j].q;
-        const unsigned src = (el.ginv[e] * k) & (2 * n - 1);
+        const unsigned src = (el.ginv[e] * k) & (2 * n - 1);      // (k_galois_digits' gather, written out: see bfv_eval_arith.cuh)
         u64 v = a[((size_t)z * (r + 1) + j) * n + (src & (n - 1))];
         v = v >= q ? v - q : v;
         v = src >= n && v ? q - v : v;
         x = add_mod(x, v, q);
     }
     out[(ehz * (r + 1) + j) * n + k] = x;
-}
-
-unsigned log2_of(unsigned n)
-{
-    unsigned lg = 0;
-    while ((1u << lg) < n) lg++;
-    return lg;
 }
 
 }  // namespace

@@ -206,6 +206,25 @@ class BFVEvaluator:
         from . import _ptr_n
         return _ptr_n(t, int(polys) * self.n, self.device)
 
+    def _ct(self, count, comps=2):
+        """polynomials of a ciphertext batch [comps][count][num_primes][n]"""
+        return comps * count * self.num_primes
+
+    def _keys(self, num=1):
+        """polynomials of `num` relinearization or galois keys [r][2][num_primes][n]"""
+        return num * 2 * self.r * self.num_primes
+
+    def _plain(self, count):
+        """polynomials of `count` plaintexts in the NTT domain, [count][r][n]"""
+        return count * self.r
+
+    @staticmethod
+    def _elems(gs):
+        """(the Galois elements as a C array of unsigned, their number)"""
+        import ctypes
+        gs = [int(g) for g in gs]
+        return (ctypes.c_uint * max(1, len(gs)))(*gs), len(gs)
+
     def _launch(self, fn, count, scratch, stream):
         """fn(scratch pointer, stream handle).  Without `scratch` the buffer comes from torch's caching allocator ON THE LAUNCH STREAM
         and lives until the call is enqueued: freed afterwards, it returns to that stream's pool, where only work ordered after
@@ -226,7 +245,7 @@ class BFVEvaluator:
     def relin_keygen(self, rlk, secret_key, a, e, stream=None):
         from . import lib, _check, _stream
         R, r = self.num_primes, self.r
-        _check(lib().mi355ntt_bfv_relin_keygen(self._h, self._p(rlk, 2 * r * R), self._p(secret_key, R), self._p(a, r * R), self._p(e, r * R),
+        _check(lib().mi355ntt_bfv_relin_keygen(self._h, self._p(rlk, self._keys()), self._p(secret_key, R), self._p(a, r * R), self._p(e, r * R),
                                                _stream(stream)), "mi355ntt_bfv_relin_keygen")
 
     @property
@@ -236,63 +255,61 @@ class BFVEvaluator:
     def relin_keygen_rns(self, rlk, secret_key, rnd, temp, nonce, stream=None):
         """the complete relinearization key generation; `nonce` has no default: a fresh one per key"""
         from . import lib, _check, _byte_ptr, _stream
-        R, r = self.num_primes, self.r
+        R = self.num_primes
         assert rnd.numel() >= self.relin_random_bytes
-        _check(lib().mi355ntt_bfv_relin_keygen_rns(self._h, self._p(rlk, 2 * r * R), self._p(secret_key, R), _byte_ptr(rnd), self._p(temp, R),
+        _check(lib().mi355ntt_bfv_relin_keygen_rns(self._h, self._p(rlk, self._keys()), self._p(secret_key, R), _byte_ptr(rnd), self._p(temp, R),
                                                    int(nonce), _stream(stream)), "mi355ntt_bfv_relin_keygen_rns")
 
     def add(self, c, a, b, count=1, stream=None):
         from . import lib, _check, _stream
-        w = 2 * count * self.num_primes
+        w = self._ct(count)
         _check(lib().mi355ntt_bfv_add(self._h, self._p(c, w), self._p(a, w), self._p(b, w), int(count), _stream(stream)), "mi355ntt_bfv_add")
 
     def sub(self, c, a, b, count=1, stream=None):
         from . import lib, _check, _stream
-        w = 2 * count * self.num_primes
+        w = self._ct(count)
         _check(lib().mi355ntt_bfv_sub(self._h, self._p(c, w), self._p(a, w), self._p(b, w), int(count), _stream(stream)), "mi355ntt_bfv_sub")
 
     def multiply(self, c3, a, b, count=1, scratch=None, stream=None):
         from . import lib, _check
-        R = self.num_primes
-        args = (self._p(c3, 3 * count * R), self._p(a, 2 * count * R), self._p(b, 2 * count * R), int(count))
+        args = (self._p(c3, self._ct(count, 3)), self._p(a, self._ct(count)), self._p(b, self._ct(count)), int(count))
         self._launch(lambda scr, s: _check(lib().mi355ntt_bfv_multiply(self._h, *args, scr, s), "mi355ntt_bfv_multiply"), count, scratch, stream)
 
     def relinearize(self, c, c3, rlk, count=1, scratch=None, stream=None):
         from . import lib, _check
-        R = self.num_primes
-        args = (self._p(c, 2 * count * R), self._p(c3, 3 * count * R), self._p(rlk, 2 * self.r * R), int(count))
+        args = (self._p(c, self._ct(count)), self._p(c3, self._ct(count, 3)), self._p(rlk, self._keys()), int(count))
         self._launch(lambda scr, s: _check(lib().mi355ntt_bfv_relinearize(self._h, *args, scr, s), "mi355ntt_bfv_relinearize"), count, scratch,
                      stream)
 
     def multiply_relin(self, c, a, b, rlk, count=1, scratch=None, stream=None):
         from . import lib, _check
-        R = self.num_primes
-        args = (self._p(c, 2 * count * R), self._p(a, 2 * count * R), self._p(b, 2 * count * R), self._p(rlk, 2 * self.r * R), int(count))
+        w = self._ct(count)
+        args = (self._p(c, w), self._p(a, w), self._p(b, w), self._p(rlk, self._keys()), int(count))
         self._launch(lambda scr, s: _check(lib().mi355ntt_bfv_multiply_relin(self._h, *args, scr, s), "mi355ntt_bfv_multiply_relin"), count,
                      scratch, stream)
 
     def add_plain(self, c, a, m, count=1, stream=None):
         """c = (c0 + E(m), c1), E(m) encryption's encoding of m"""
         from . import lib, _check, _stream
-        w = 2 * count * self.num_primes
+        w = self._ct(count)
         _check(lib().mi355ntt_bfv_add_plain(self._h, self._p(c, w), self._p(a, w), self._p(m, count), int(count), _stream(stream)),
                "mi355ntt_bfv_add_plain")
 
     def sub_plain(self, c, a, m, count=1, stream=None):
         from . import lib, _check, _stream
-        w = 2 * count * self.num_primes
+        w = self._ct(count)
         _check(lib().mi355ntt_bfv_sub_plain(self._h, self._p(c, w), self._p(a, w), self._p(m, count), int(count), _stream(stream)),
                "mi355ntt_bfv_sub_plain")
 
     def plain_ntt(self, mhat, m, count=1, stream=None):
         """mhat [count][r][n]: the centred lift of m in the NTT domain over Q, the operand of multiply_plain_ntt"""
         from . import lib, _check, _stream
-        _check(lib().mi355ntt_bfv_plain_ntt(self._h, self._p(mhat, count * self.r), self._p(m, count), int(count), _stream(stream)),
+        _check(lib().mi355ntt_bfv_plain_ntt(self._h, self._p(mhat, self._plain(count)), self._p(m, count), int(count), _stream(stream)),
                "mi355ntt_bfv_plain_ntt")
 
     def multiply_plain(self, c, a, m, count=1, scratch=None, stream=None):
         from . import lib, _check
-        w = 2 * count * self.num_primes
+        w = self._ct(count)
         args = (self._p(c, w), self._p(a, w), self._p(m, count), int(count))
         self._launch(lambda scr, s: _check(lib().mi355ntt_bfv_multiply_plain(self._h, *args, scr, s), "mi355ntt_bfv_multiply_plain"), count,
                      scratch, stream)
@@ -300,8 +317,8 @@ class BFVEvaluator:
     def multiply_plain_ntt(self, c, a, mhat, count=1, shared=False, scratch=None, stream=None):
         """shared=False: mhat [count][r][n], one plaintext per ciphertext; shared=True: mhat [r][n] for the whole batch"""
         from . import lib, _check
-        w = 2 * count * self.num_primes
-        args = (self._p(c, w), self._p(a, w), self._p(mhat, (1 if shared else count) * self.r), int(count), 1 if shared else 0)
+        w = self._ct(count)
+        args = (self._p(c, w), self._p(a, w), self._p(mhat, self._plain(1 if shared else count)), int(count), 1 if shared else 0)
         self._launch(lambda scr, s: _check(lib().mi355ntt_bfv_multiply_plain_ntt(self._h, *args, scr, s), "mi355ntt_bfv_multiply_plain_ntt"),
                      count, scratch, stream)
 
@@ -309,7 +326,7 @@ class BFVEvaluator:
         """key for Galois element g from explicit samples (as relin_keygen)"""
         from . import lib, _check, _stream
         R, r = self.num_primes, self.r
-        _check(lib().mi355ntt_bfv_galois_keygen(self._h, self._p(gk, 2 * r * R), self._p(secret_key, R), int(g), self._p(a, r * R),
+        _check(lib().mi355ntt_bfv_galois_keygen(self._h, self._p(gk, self._keys()), self._p(secret_key, R), int(g), self._p(a, r * R),
                                                 self._p(e, r * R), _stream(stream)), "mi355ntt_bfv_galois_keygen")
 
     def galois_random_bytes(self, num_g=1):
@@ -318,22 +335,19 @@ class BFVEvaluator:
     def galois_keygen_rns(self, gk, secret_key, gs, rnd, temp, nonce, stream=None):
         """the complete key generation for the elements gs, gk [len(gs)][r][2][num_primes][n]; `nonce` has no default: a fresh one per
         call"""
-        import ctypes
         from . import lib, _check, _byte_ptr, _stream
-        R, r = self.num_primes, self.r
-        gs = [int(g) for g in gs]
-        assert rnd.numel() >= self.galois_random_bytes(len(gs))
-        arr = (ctypes.c_uint * max(1, len(gs)))(*gs)
-        _check(lib().mi355ntt_bfv_galois_keygen_rns(self._h, self._p(gk, len(gs) * 2 * r * R), self._p(secret_key, R), arr, len(gs),
+        R = self.num_primes
+        arr, num = self._elems(gs)
+        assert rnd.numel() >= self.galois_random_bytes(num)
+        _check(lib().mi355ntt_bfv_galois_keygen_rns(self._h, self._p(gk, self._keys(num)), self._p(secret_key, R), arr, num,
                                                     _byte_ptr(rnd), self._p(temp, R), int(nonce), _stream(stream)),
                "mi355ntt_bfv_galois_keygen_rns")
 
     def apply_galois(self, c, a, gk, g, count=1, scratch=None, stream=None):
         """c = tau_g(a) key-switched back to s with g's key gk"""
         from . import lib, _check
-        R = self.num_primes
-        w = 2 * count * R
-        args = (self._p(c, w), self._p(a, w), self._p(gk, 2 * self.r * R), int(g), int(count))
+        w = self._ct(count)
+        args = (self._p(c, w), self._p(a, w), self._p(gk, self._keys()), int(g), int(count))
         self._launch(lambda scr, s: _check(lib().mi355ntt_bfv_apply_galois(self._h, *args, scr, s), "mi355ntt_bfv_apply_galois"), count,
                      scratch, stream)
 
@@ -347,25 +361,18 @@ class BFVEvaluator:
         """c_out [len(gs)][2][count][num_primes][n]: batch k = H_{gs[k]}(a), the automorphism with the digits of a's c1 split and
         transformed once for all elements; gk [len(gs)][r][2][num_primes][n] as galois_keygen_rns writes it for gs.  c_out must not
         overlap a.  Not word for word apply_galois (another valid digit decomposition); decrypts to the same plaintext."""
-        import ctypes
         from . import lib, _check
-        R = self.num_primes
-        gs = [int(g) for g in gs]
-        arr = (ctypes.c_uint * max(1, len(gs)))(*gs)
-        args = (self._p(c_out, len(gs) * 2 * count * R), self._p(a, 2 * count * R), self._p(gk, len(gs) * 2 * self.r * R), arr, len(gs),
-                int(count))
+        arr, num = self._elems(gs)
+        args = (self._p(c_out, num * self._ct(count)), self._p(a, self._ct(count)), self._p(gk, self._keys(num)), arr, num, int(count))
         self._launch(lambda scr, s: _check(lib().mi355ntt_bfv_apply_galois_hoisted(self._h, *args, scr, s),
                                            "mi355ntt_bfv_apply_galois_hoisted"), count, scratch, stream)
 
     def galois_sum(self, c, a, gk, gs, count=1, weights=None, scratch=None, stream=None):
         """c = sum_k w_k H_{gs[k]}(a), summed in the NTT domain; weights [len(gs)][r][n] from plain_ntt(count=len(gs)), shared by the
         batch, or None for every w_k = 1.  c may alias a."""
-        import ctypes
         from . import lib, _check, vp
-        R = self.num_primes
-        gs = [int(g) for g in gs]
-        arr = (ctypes.c_uint * max(1, len(gs)))(*gs)
-        w = vp(0) if weights is None else self._p(weights, len(gs) * self.r)
-        args = (self._p(c, 2 * count * R), self._p(a, 2 * count * R), self._p(gk, len(gs) * 2 * self.r * R), arr, len(gs), w, int(count))
+        arr, num = self._elems(gs)
+        w = vp(0) if weights is None else self._p(weights, self._plain(num))
+        args = (self._p(c, self._ct(count)), self._p(a, self._ct(count)), self._p(gk, self._keys(num)), arr, num, w, int(count))
         self._launch(lambda scr, s: _check(lib().mi355ntt_bfv_galois_sum(self._h, *args, scr, s), "mi355ntt_bfv_galois_sum"), count,
                      scratch, stream)
