@@ -258,25 +258,13 @@ hipError_t fast_tables_create(FastTables* t, unsigned n, unsigned num_primes, co
         if (hl < t->hl) t->hl = hl;
         PrimeDev& d = pd[i];
         d.q = pp.q;
-        d.nq = 0ULL - pp.q;
         d.si = split_inv ? mulmod(split_inv[i], (pp.q >> 1) + 1, pp.q) : 0;       // (... and its inverse counterpart, times 2^-1)
         d.si_p = split_inv ? shoup(d.si, pp.q) : 0;
         d.sf = split_fwd ? split_fwd[i] : 0;                   // (n = 2^16 contexts: the stage that couples the two halves)
         d.sf_p = split_fwd ? shoup(split_fwd[i], pp.q) : 0;
         d.mu = pp.mu;
         d.k = pp.k;
-        const unsigned g = pp.k - 1 < 16 ? pp.k - 1 : 16;
-        d.red_sh1 = pp.k - 1 - g;
-        d.red_sh2 = g;
-        d.red_c = (u32)((((u128)1) << (31 + pp.k)) / pp.q);
-        // near-2^k shape: q = 2^k - delta, k > 32, delta < 2^24 and 2^(64-k) * delta + 2 * delta < 2^k (reduce_2q_near)
-        const u128 dl = (((u128)1) << pp.k) - pp.q;
-        // ... and 2 delta^2 + 3 delta < 2^k (mul_fold_near: the fused products' fold multiplication)
-        const bool near_ok = pp.k > 32 && dl < ((u128)1 << 24) && ((dl << (64 - pp.k)) + 2 * dl) < (((u128)1) << pp.k) &&
-                             (2 * dl * dl + 3 * dl) < (((u128)1) << pp.k);
-        d.delta = near_ok ? (u32)dl : 0;
-        d.near_sh = pp.k > 32 ? pp.k - 32 : 0;
-        d.near_mask = pp.k > 32 ? (u32)((1ull << (pp.k - 32)) - 1) : 0;
+        const bool near_ok = prime_reduction_constants(d, pp.q, pp.k);      // nq, red_*, delta, near_* (ntt_core.cuh)
         d.lit = (literal && !pp.barrett_exact) ? 1u : 0u;
         d.twn[0] = TwPair{pp.ninv, shoup(pp.ninv, pp.q)};
         for (unsigned j = 1; j < 32; j++) {                   // (n >= 2048: the entries exist)

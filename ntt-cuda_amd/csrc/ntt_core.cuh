@@ -60,6 +60,27 @@ struct PrimeDev {
     TwPair twn[32];
 };
 
+// The reduction constants of a k-bit modulus q -- nq, red_sh1, red_sh2, red_c (reduce_2q), delta, near_sh, near_mask (reduce_2q_near,
+// mul_fold_near) -- derived in ONE place: fast_tables_create and the primitives' probe (tests/cpp/lazy_probe.hip) both call it.
+// Returns whether q has the near-2^k shape (delta is 0 when it has not).
+__host__ inline bool prime_reduction_constants(PrimeDev& d, u64 q, u32 k)
+{
+    d.nq = 0ULL - q;
+    const unsigned g = k - 1 < 16 ? k - 1 : 16;
+    d.red_sh1 = k - 1 - g;
+    d.red_sh2 = g;
+    d.red_c = (u32)((((u128)1) << (31 + k)) / q);
+    // near-2^k shape: q = 2^k - delta, k > 32, delta < 2^24 and 2^(64-k) * delta + 2 * delta < 2^k (reduce_2q_near)
+    const u128 dl = (((u128)1) << k) - q;
+    // ... and 2 delta^2 + 3 delta < 2^k (mul_fold_near: the fused products' fold multiplication)
+    const bool near_ok = k > 32 && dl < ((u128)1 << 24) && ((dl << (64 - k)) + 2 * dl) < (((u128)1) << k) &&
+                         (2 * dl * dl + 3 * dl) < (((u128)1) << k);
+    d.delta = near_ok ? (u32)dl : 0;
+    d.near_sh = k > 32 ? k - 32 : 0;
+    d.near_mask = k > 32 ? (u32)((1ull << (k - 32)) - 1) : 0;
+    return near_ok;
+}
+
 // Checked raw calls (kernels.hpp, kGuardBit): the record in front of the PrimeDev array holds {current epoch, epoch of the
 // last table mismatch}.  Returns true when this launch must not touch the data; clears the flag bit of prime_base.
 __device__ __forceinline__ bool guard_says_skip(const PrimeDev* primes, unsigned& prime_base)
