@@ -33,24 +33,30 @@ class HoistModel(GaloisModel):
                 acc[h] = acc[h] + d * _obj(gk_k[i, h, j])
         return acc
 
-    def hoisted(self, c, gk_k, g, hoist=None):
+    def terms(self, c, gks, gs):
+        """[k][j]: _term of element gs[k] with its key gks[k] for prime j -- what hoisted and galois_sum of the same elements share
+        (pass it to them as term / terms: the r^2 wide products per element and prime are most of the model's time)"""
+        hoist = self.hoist(c)
+        return [[self._term(hoist, gks[k], g, j) for j in range(self.r)] for k, g in enumerate(gs)]
+
+    def hoisted(self, c, gk_k, g, hoist=None, term=None):
         """H_g(c) with g's key gk_k [r][2][R][n]"""
-        hoist = self.hoist(c) if hoist is None else hoist
+        hoist = self.hoist(c) if hoist is None and term is None else hoist
         out = self._out(2)
         for j, (q, w) in enumerate(zip(self.qs, self.psis)):
-            acc = self._term(hoist, gk_k, g, j)
+            acc = self._term(hoist, gk_k, g, j) if term is None else term[j]
             for h in range(2):
                 out[h, j] = self.inv((acc[h] % q).astype(np.uint64), q, w)
         return out
 
-    def galois_sum(self, c, gks, gs, weights=None):
+    def galois_sum(self, c, gks, gs, weights=None, terms=None):
         """sum_k w_k H_{gs[k]}(c); gks [G][r][2][R][n], weights [G][r][n] (plain_ntt per element) or None for every w_k = 1"""
-        hoist = self.hoist(c)
+        hoist = self.hoist(c) if terms is None else None
         out = self._out(2)
         for j, (q, w) in enumerate(zip(self.qs, self.psis)):
             tot = [np.zeros(self.n, dtype=object), np.zeros(self.n, dtype=object)]
             for k, g in enumerate(gs):
-                acc = self._term(hoist, gks[k], g, j)
+                acc = self._term(hoist, gks[k], g, j) if terms is None else terms[k][j]
                 wk = 1 if weights is None else _obj(weights[k][j])
                 for h in range(2):
                     tot[h] = tot[h] + acc[h] * wk

@@ -216,7 +216,8 @@ def primes_at(native, n, count, seed=41):
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,r", [(8192, 3), (16384, 3), (32768, 15), (65536, 2)])
 def test_ring_degrees(native, oracle, gpu, n, r):
-    """multiply, relinearize, apply_galois; n = 32768 is the whole 16-prime demo set; n = 65536 has no demo roots, so 61-bit primes
+    """multiply, relinearize, apply_galois; the hoisted automorphisms and their sums (galois_slot depends on log2 n) at every degree
+    the hoisted tests leave out; n = 32768 is the whole 16-prime demo set; n = 65536 has no demo roots, so 61-bit primes
     = 1 (mod 2^31) found here"""
     if n == 65536:
         qs, psis = primes_at(native, n, r + 1)
@@ -225,7 +226,7 @@ def test_ring_degrees(native, oracle, gpu, n, r):
     else:
         qs, psis = demo_subset(n, r)
     S = Sch(native, oracle, n, qs, psis, 1024)
-    compare(S, 1 if n >= 32768 else 2, ("mul", "galois"))
+    compare(S, 1 if n >= 32768 else 2, ("mul", "galois") if n == 32768 else ("mul", "galois", "hoist"))
     S.close()
 
 
