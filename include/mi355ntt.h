@@ -376,7 +376,10 @@ int mi355ntt_bfv_decrypt_batch(const mi355ntt_bfv* bfv, mi355ntt_u64* d_c, const
 /* ---- samplers and the complete drivers --------------------------------------------------
  * generate_random / generate_random_default (distributions.cuh:192-276): Salsa20/20 keystream, floor(nbytes / 64)
  * blocks written to d_out (16-byte aligned), 64-bit nonce, block counter from 0.  The reference uses key = 32 x 0x01
- * (_default) or 32 x 77, nonce 0 -- the same stream on every call; pass a fresh nonce per call for anything real. */
+ * (_default), nonce 0 -- the same stream on every call; pass a fresh nonce per call for anything real.  generate_random
+ * fills 32 bytes with 77 but uploads 24 of them (XSALSA20_CRYPTO_NONCEBYTES, distributions.cuh:232-235): its effective key
+ * is 24 x 77 followed by what the constant array held before -- 8 x 0 in a fresh process, 8 x 0x01 after a call of
+ * generate_random_default (recorded from the reference binary: tests/golden/ref_words.npz, samplers/generate_random-*). */
 int mi355ntt_salsa20_keystream(void* d_out, size_t nbytes, const unsigned char* key32, mi355ntt_u64 nonce, mi355ntt_stream stream);
 /* bytes of keystream keygen_rns / encryption_rns consume (bfv_keygen.cuh:99, bfv_encryption.cuh:228) */
 size_t mi355ntt_bfv_keygen_random_bytes(const mi355ntt_bfv* bfv);

@@ -9,8 +9,10 @@
  * Pinning: checked against the reference's only known-answer test
  * (decryption_test.cu:348,355 -> m[i] = i % 10, decryption_test.cu:230-232) and the
  * known-answer constants in parameter.h:31-79 / old/decryption.cu / old/encryption.cu
- * (see tests/test_oracle_golden.py).  The reference itself cannot be built here
- * (CUDA + PTX, needs cuda_runtime.h), so there is no oracle/_ref.
+ * (see tests/test_oracle_golden.py), and held word for word to what the reference's own
+ * kernels return: tests/golden/ref_words.npz was recorded from oracle/_ref (the reference built
+ * for gfx950 by `make ref`; ref_port.py, ref_shim.h) and tests/test_reference_words_host.py
+ * replays it against this library on every CPU run.
  *
  * Every function cites the reference file:line it follows (paths relative to
  * the reference's BFV_Scheme/).

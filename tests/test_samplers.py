@@ -10,7 +10,7 @@ ECRYPT_KEY = bytes([0x80] + [0] * 31)        # ECRYPT Salsa20/20, 256-bit key, s
 ECRYPT_STREAM0 = bytes.fromhex("E3BE8FDD8BECA2E3EA8EF9475B29A6E7003951E1097A5C38D23B7A5FAD9F6844"
                                "B22C97559E2723C7CBBD3FE4FC8D9A0744652A83E72A9C461876AF4D7EF1A117")
 DEFAULT_KEY = bytes([1] * 32)                # generate_random_default, distributions.cuh:236
-OTHER_KEY = bytes([77] * 32)                 # generate_random, distributions.cuh:206
+OTHER_KEY = bytes([77] * 32)                 # generate_random's fill value (it uploads 24 of these bytes: tests/ref_words_cases.py)
 
 
 def salsa20_block_py(key, nonce, ctr):
